@@ -15,7 +15,7 @@ not shipped; the bench builds the equivalent starting point with ``--pretrain-ro
 Rounds then start at 201, so with the default ``--warmup 2`` the timed window 203..210
 contains all four poison rounds.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     # one rank per GPU over RCCL
     python bench.py --emulate-rank R --emulate-world N    # rank R's share of N, on one GPU
 
@@ -24,6 +24,12 @@ Launch forms.  Under a launcher (``WORLD_SIZE`` set, torchrun) every process is 
 and ``--gpus N > 1`` this process is only a PARENT: it never imports the framework or touches
 the GPU, starts ``python -m torch.distributed.run --nproc-per-node N`` as a child (N fresh
 rank processes), relays rank 0's JSON line and exits with the child's status.
+
+A plain run does only what the headline figure needs: setup (data, model, the untimed warm
+start), W warmup rounds, K timed rounds, the JSON line.  ``--dump-outputs DIR`` then writes what
+the last timed round returned (``_dump_outputs``).  ``--full`` is where measurements beyond the
+headline belong (secondary configs and per-kernel figures are separate tools under
+``dba_mod_amd/tools`` and ``scripts/gpu``, so today it adds nothing).
 
 Strong scaling: the round's work is fixed; N GPUs split its clients (LPT) and its
 evaluation images.
@@ -125,7 +131,40 @@ def _args(argv=None):
                     help="rank 0 saves the final global model here (torch.save; cross-world tests)")
     ap.add_argument("--round-phases", action="store_true",
                     help="add every timed round's host phase times (s) to the JSON line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed round returned (the global model and the "
+                         "round's test results) as DIR/<name>.npy after the timed window")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that are not part of the headline figure (none "
+                         "today: a plain run already does only setup, warmup and the timed rounds)")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 48 << 20      # per array; every dump stays well under 64 MB in all
+
+
+def _dump_outputs(folder: str, server, done) -> None:
+    """What a caller of the timed path holds after its last round, as float32 / float64 .npy:
+    the aggregated global model (``Server.global_state``; a fixed seeded sample of its
+    elements when it is larger than DUMP_MAX_BYTES) and the summaries ``Server.run_rounds``
+    returned (the last round's global test results, and accuracy / ASR of every timed round).
+    Inputs are seeded by the config, so equal arguments give comparable dumps across builds."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    state = server.global_state.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1)
+    keep = DUMP_MAX_BYTES // 4
+    if state.size > keep:
+        state = state[np.sort(np.random.RandomState(0).choice(state.size, keep, replace=False))]
+    np.save(os.path.join(folder, "global_state.npy"), state)
+    last = done[-1] if done else {}
+    trig = last.get("trigger_asr", {})
+    np.save(os.path.join(folder, "last_round.npy"),
+            np.array([float(last.get(k, 0.0) or 0.0) for k in ("epoch", "global_acc", "global_loss", "global_asr",
+                                                              "poison_loss")]
+                     + [float(trig[k]) for k in sorted(trig)], dtype=np.float64))
+    np.save(os.path.join(folder, "rounds.npy"),
+            np.array([[float(r["epoch"]), float(r.get("global_acc", 0.0)), float(r.get("global_asr", 0.0))]
+                      for r in done], dtype=np.float64).reshape(-1, 3))
 
 
 def main(argv=None) -> int:
@@ -201,6 +240,8 @@ def _run(args) -> int:
     state_sha = hashlib.sha256(server.global_state.detach().cpu().numpy().tobytes()).hexdigest()[:16]
     if args.dump_state and (dctx.is_main or dctx.emulated):
         torch.save(server.global_state.detach().cpu(), args.dump_state)
+    if args.dump_outputs and (dctx.is_main or dctx.emulated):
+        _dump_outputs(args.dump_outputs, server, done)
     comm_kinds = sorted({k for r in done for k in r.get("comm_bytes", {})})
     comm_mean = {k: int(round(sum(r.get("comm_bytes", {}).get(k, 0) for r in done) / max(1, len(done))))
                  for k in comm_kinds}

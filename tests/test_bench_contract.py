@@ -38,8 +38,22 @@ def _check(out, n):
     assert sum(rm) <= out["ms_per_step"] * 2 * 1.05
 
 
-def test_bench_world1_cpu():
-    _check(_run([sys.executable, "bench.py", *SMALL]), 1)
+def test_bench_world1_cpu(tmp_path):
+    """Also ``--dump-outputs``: what the last timed round returned, as float32 / float64 .npy
+    that agree with the JSON line."""
+    import numpy as np
+    out = _run([sys.executable, "bench.py", *SMALL, "--dump-outputs", str(tmp_path / "dump")])
+    _check(out, 1)
+    dump = {n: np.load(tmp_path / "dump" / n) for n in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(dump) == ["global_state.npy", "last_round.npy", "rounds.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    state = dump["global_state.npy"]
+    assert state.dtype == np.float32 and state.ndim == 1 and state.size > 0 and np.isfinite(state).all()
+    assert dump["rounds.npy"].shape == (2, 3)
+    assert [[int(e), round(a, 2), round(s, 2)] for e, a, s in dump["rounds.npy"]] == out["rounds"]
+    assert dump["last_round.npy"][0] == out["rounds"][-1][0]
+    assert round(dump["last_round.npy"][1], 3) == out["global_acc"]
 
 
 def test_bench_torchrun_world2_cpu():
@@ -64,7 +78,7 @@ def test_bench_self_spawn_world4_cpu():
     assert out["collective_selfcheck_ok"] is True and out["rccl_ok"] is None
     assert len(out["devices"]) == 4
     assert out["comm_bytes_per_round"].get("all_reduce", 0) > 0
-    one = _run([sys.executable, "bench.py", *SMALL])
+    one = _run([sys.executable, "bench.py", *SMALL, "--full"])      # --full changes no headline field
     assert one["world"] == 1 and one["dist_backend"] == "none" and one["comm_bytes_per_round"] == {}
     assert out["rounds"] == one["rounds"]
 
