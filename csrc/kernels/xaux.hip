@@ -1,5 +1,6 @@
 // fp32 family, operand helpers: fp16-pair weight planes split once per fold / step (single and
-// batched), and the operand max |x| slots (segment and per-replica forms).
+// batched), their fragment-ordered form for the whole-image evaluation conv, and the operand
+// max |x| slots (segment and per-replica forms).
 #include "common.hpp"
 #include "xmfma.hpp"
 #include <algorithm>
@@ -54,6 +55,37 @@ __global__ __launch_bounds__(256) void xsplit_w_batch_kernel(const XSBatch b) {
   const long long e1 = e0 + kXSChunk < d.per ? e0 + kXSChunk : d.per;
   xsplit_w_body((const float*)d.w, d.sstride, d.per, (const int*)d.amax, (int)d.ld, (uint16_t*)d.out, blockIdx.y, e0,
                 e1, 1024);
+}
+
+// the planes of 3x3 weights [Ncol][9][Cs] (Ncol, Cs multiples of 32) in the order a wave of the
+// whole-image conv consumes them (xconv_fwd.hip ximg2_kernel): per slot, for each (32-column tile
+// nt, k-step t = chunk * 9 + tap, half-step kk, plane p) one contiguous 1-KB block holding lane
+// l's 16 bytes (column nt * 32 + (l & 31), elements (kk * 2 + (l >> 5)) * 8 .. + 7 of the chunk)
+// at 16 l — the values untouched, one buffer_load_dwordx4 per B fragment.  Once per fold, one
+// launch per 24 weights (blockIdx.y = slot; one thread per 16 bytes, desc i owns blocks [boff_i,
+// boff_{i+1}))
+struct XFDesc {   // all int64 (built from a torch int64 host tensor)
+  long long planes, out, ncol, cs, boff;
+};
+struct XFBatch {
+  XFDesc d[kXSBatch];
+  int n;
+};
+__global__ __launch_bounds__(256) void xfrag_w_kernel(const XFBatch b) {
+  int i = 0;
+  while (i + 1 < b.n && (long long)blockIdx.x >= b.d[i + 1].boff) ++i;
+  const XFDesc& d = b.d[i];
+  const int Cs = (int)d.cs, K = 9 * Cs, NK = K / 32;
+  const long long per = d.ncol * K;
+  const long long idx = ((long long)blockIdx.x - d.boff) * 256 + threadIdx.x;   // output 16-B unit
+  if (idx >= per / 4) return;
+  const int l = (int)(idx & 63), f = (int)(idx >> 6) & 3, p = f & 1, kk = f >> 1;
+  const long long tt = idx >> 8;
+  const int t = (int)(tt % NK), nt = (int)(tt / NK), cc = t / 9, tap = t - cc * 9;
+  const long long e = (long long)(nt * 32 + (l & 31)) * K + tap * Cs + cc * 32 + (kk * 2 + (l >> 5)) * 8;
+  const uint16_t* __restrict__ src = (const uint16_t*)d.planes + ((long long)blockIdx.y * 2 + p) * per;
+  uint16_t* __restrict__ dst = (uint16_t*)d.out + (long long)blockIdx.y * 2 * per;
+  ((uint4*)dst)[idx] = *(const uint4*)(src + e);
 }
 
 // max |x| of n segments (offset, length) of every replica's flat row (the conv weights of a
@@ -144,6 +176,30 @@ DBA_EXPORT int dba_xsplit_w_batch(const void* desc, int n, int slots, void* stre
       nb += (b.d[i].per + kXSChunk - 1) / kXSChunk;
     }
     hipLaunchKernelGGL(xsplit_w_batch_kernel, dim3((unsigned)nb, slots), dim3(256), 0, (hipStream_t)stream, b);
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+// the fragment-ordered planes (xfrag_w_kernel) of n split 3x3 weight operands in one launch per
+// 24; desc: n x XFDesc in HOST memory (passed by value): planes [slots][2][ncol * 9 * cs] fp16
+// (dba_xsplit_w), out the same size, both 16-B aligned
+
+DBA_EXPORT int dba_xfrag_w_batch(const void* desc, int n, int slots, void* stream) {
+  const XFDesc* ds = (const XFDesc*)desc;
+  for (int i0 = 0; i0 < n; i0 += kXSBatch) {
+    XFBatch b{};
+    b.n = std::min(kXSBatch, n - i0);
+    long long nb = 0;
+    for (int i = 0; i < b.n; ++i) {
+      b.d[i] = ds[i0 + i];
+      if (b.d[i].ncol <= 0 || b.d[i].cs <= 0 || b.d[i].ncol % 32 || b.d[i].cs % 32 || ((b.d[i].planes | b.d[i].out) & 15))
+        return -105;
+      b.d[i].boff = nb;
+      nb += b.d[i].ncol * 9 * b.d[i].cs / 1024;
+    }
+    hipLaunchKernelGGL(xfrag_w_kernel, dim3((unsigned)nb, slots), dim3(256), 0, (hipStream_t)stream, b);
     const int rc = (int)hipGetLastError();
     if (rc != 0) return rc;
   }

@@ -85,6 +85,8 @@ struct XArgs {
   int amax_src_ld, amax_w_ld, amax_out_ld;
   const uint16_t* wp;                        // the weights pre-split (xsplit_w_kernel): per slot
   long long wp_sstride;                      //    2 planes of wp_sstride/2 fp16, scaled like amax_w
+  const uint16_t* wf;                        // the same planes fragment-ordered (xfrag_w_kernel): the
+  long long wf_sstride;                      //    whole-image conv's B operand (ximg2_kernel), per slot
   // in-launch split-K combine (xconv_kernel sk_combine): slab z of replica g at
   // sk_ws + z * zstride + g * sk_gstride; sk_cnt: zeroed arrival counters, one per
   // (replica, tile, class); out / out_gstride stay the real output

@@ -1,6 +1,8 @@
 // fp32 family, forward pass (xconv.hpp): the conv launcher (halo / whole-image / implicit-GEMM
 // tiles, split-K in-launch or in-block, fused training-BN statistics and lazy BN operands), the
-// evaluation down-block, and the whole-image halo conv of the 8 / 4-wide evaluation stages.
+// evaluation down-block, and the whole-image halo conv of the 8 / 4-wide evaluation stages in its
+// two forms (ximg2_kernel: B fragments from global memory, two patch buffers; ximg_kernel: the
+// LDS weight ring).
 #include "xhalo.hpp"
 
 namespace xg {
@@ -13,22 +15,26 @@ SplitPolicy& split_policy() {
 namespace {
 
 // ================================================================ whole-image halo conv
-// Stride-1 3x3 pad-1 evaluation forward of the small-image stages (W 16 / 8 / 4: ResNet stages
-// 2-4 on 32x32 inputs; fp16 pair, weights pre-split at the eval fold).  The implicit GEMM
+// (The first form: since ximg2_kernel below it runs only for weights without fragment-ordered
+// planes — fp32 weights split while staging, PRE false — and as dba_ximg_set(2), the bit-equality
+// test's and the kernel bench's A/B.)
+// Stride-1 3x3 pad-1 evaluation forward of the small-image stages (W 8 / 4: ResNet stages
+// 3-4 on 32x32 inputs; fp16 pair, weights pre-split at the eval fold).  The implicit GEMM
 // re-fetches every input element once per tap, and at these shapes its operand fetch — not
 // the MFMA — bounds it (eval.layer3 / 4 ran +37 / +43 % faster with the in-loop global loads
 // removed, against +5 % without the in-loop barriers: profiles/r4/ximg).  Here a block owns
-// IMGS whole images (BM = 128 or 256 output pixels) x BN output channels; the reduction runs
+// IMGS whole images (BM = 128 output pixels) x BN output channels; the reduction runs
 // channel-chunk-major (chunk of 32 channels, then its 9 taps): each chunk's zero-padded patch
 // (IMGS x (W+2)^2 pixels x 32 channels) is loaded once, split once into the LDS patch, and
 // read by all 9 taps at their pixel offsets — (W+2)^2 / W^2 = 1.27x / 1.56x / 2.25x of the
-// image bytes instead of 9x.  The next chunk's patch is loaded into registers while the
+// image bytes (W 16 / 8 / 4) instead of 9x.  The next chunk's patch is loaded into registers while the
 // current chunk's 9 k-steps run (8 steps to land).
 // 4 waves, 2 blocks per CU, one patch buffer: the next chunk is split + stored after the
 // chunk's last barrier (one more barrier per chunk).  (An 8-wave BM-256 form with two patch
 // buffers, the next chunk split in the MFMA gaps, was measured slower — one block per CU
 // exposes its prologue / epilogue: eval.layer3 254 vs 314 TF, profiles/r4/ximg/README.md.)
-// Weights: the two-stage register / LDS ring of xhalo_kernel.  Epilogue straight from the
+// Weights: the two-stage register / LDS ring of xhalo_kernel, one barrier per k-step (global ->
+// VGPR -> LDS -> VGPR in every block: ximg2_kernel's first saving).  Epilogue straight from the
 // accumulators (a 32-lane row is 32 consecutive output channels: 128-B segments).
 // (A fused downsampling shortcut as extra one-tap chunks — each refilling the patch, its loads
 // prefetched only two k-steps ahead — measured slower than the shortcut conv + this kernel with a
@@ -241,9 +247,180 @@ __global__ __launch_bounds__(256) void ximg_kernel(const XArgs a) {
   if (a.amax_out) amax_fold(a.amax_out, a.amax_out_ld, g, vmax);
 }
 
-// the whole-image halo conv (ximg_kernel): evaluation forward, 3x3 stride-1 pad-1, square
-// W 8 / 4, Cs % 32 == 0, no fused BN / lazy operands (dba_ximg_set(0): off — the tests' A/B
-// against the implicit GEMM)
+// ================================================================ whole-image halo conv, 2nd form
+// ximg_kernel's tiles, patch, k order and epilogue (so every output element sees the same
+// MFMA sequence: the same bits), without its two costs that the result does not need
+// (profiles/r4/ximg: +13 / +15 % without the in-loop weight loads, +9 % without the
+// chunk-boundary refill):
+//  * B fragments come straight from global memory: the weights are fragment-ordered once at the
+//    fold (xaux.hip xfrag_w_kernel: per (32-column tile, k-step, half-step, plane) one 1-KB
+//    block, lane l's 16 B at 16 l), so a fragment is one buffer_load_dwordx4 per lane, two
+//    k-steps ahead in a 3-slot register ring — no LDS weight ring, no swizzled ds_write /
+//    ds_read of weights, no barrier per k-step.  A wave owns all 128 rows x 32 columns
+//    (WM = 1; BN 64: 2 x 2 waves of 64 x 32), so each fragment is loaded by one wave of the block.
+//  * Two patch buffers (the LDS the weight ring held): the next chunk's patch registers are
+//    split and stored into the other buffer one piece per k-step in the MFMA gaps (the fill
+//    hook of mma_half), each piece's reload for the chunk after issued right behind it.  One
+//    barrier per chunk.  W 4: 2 x 36.9 KB of dynamic LDS (two blocks per CU: 147 of 160 KB).
+// 17 x 1024 images, same box: eval.layer3 321 -> 370, eval.layer4 362 -> 417 TFLOP/s
+// (profiles/r7/ximg2/README.md).
+template <int W, int IMGS, int BN>
+__global__ __launch_bounds__(256) void ximg2_kernel(const XArgs a) {
+  constexpr int P = 2, NT = 256;
+  constexpr int PW = W + 2, PI = PW * PW, PP = IMGS * PI;   // padded pixels per image / patch
+  constexpr int CC = 32, CH = CC / 8, Q4 = CC / 4;          // chunk channels, 16-B chunks, float4 per pixel
+  constexpr int PATCH = PP * CH;                            // uint4 per plane
+  constexpr int BM = IMGS * W * W;
+  constexpr int WN = BN / 32, WM = (NT / 64) / WN, TM = BM / WM, MI = TM / 32;
+  static_assert(WM * WN == NT / 64 && MI >= 1 && BM == 128, "tiling");
+  extern __shared__ __attribute__((aligned(16))) uint4 ximg2_patch[];   // [2 buffers][P][PATCH]
+
+  const int g = blockIdx.y;
+  const int tn = blockIdx.x % a.tiles_n, tm = blockIdx.x / a.tiles_n;
+  const int img0 = tm * IMGS, n0 = tn * BN;
+  const int nv = min(valid_rows(a.nvalid, g, a.N), a.N);
+  if (img0 >= nv) return;
+  const int slot = a.wsel ? a.wsel[g] : g;
+  const int Cs = a.Cs, NC = Cs / CC, NK = 9 * NC;
+  const float* __restrict__ src = a.src + (long long)g * a.src_gstride;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+  const int fr = lane & 31, hf = lane >> 5;
+
+  // ---- patch pieces: piece u of chunk cc (zero padding / invalid images / past the last chunk)
+  constexpr int NE = (PP * Q4 + NT - 1) / NT;
+  static_assert(NE <= 9, "one patch piece per k-step");
+  float4 pv[NE];
+  const __amdgpu_buffer_rsrc_t rA = rsrc(src, (long long)a.N * W * W * Cs * 4);
+  auto pload1 = [&](int u, int cc) __attribute__((always_inline)) {
+    const int e = tid + NT * u;
+    const int pp = e / Q4, q = e - pp * Q4;
+    const int im = pp / PI, rem = pp - im * PI;
+    const int h = rem / PW - 1, w = rem % PW - 1, img = img0 + im;
+    const bool ok = e < PP * Q4 && cc < NC && img < nv && (unsigned)h < (unsigned)W && (unsigned)w < (unsigned)W;
+    pv[u] = bload4(rA, ok ? (((img * W + h) * W + w) * Cs + cc * CC + q * 4) * 4 : kOOB);
+  };
+  HScale hs;
+  auto ppiece = [&](int u, int buf) __attribute__((always_inline)) {   // piece u of pv -> patch buffer buf
+    const int e = tid + NT * u;
+    if (NT * (u + 1) > PP * Q4 && e >= PP * Q4) return;   // (only the last piece can be partial)
+    const int pp = e / Q4, q = e - pp * Q4;
+    const int prow = (pp % PI) / PW;   // patch row: the swizzle key
+    uint2 sp[P];
+    split4h(pv[u].x, pv[u].y, pv[u].z, pv[u].w, hs.ma, sp);
+    const int o = pp * CH + ((q >> 1) ^ (prow & 3));
+#pragma unroll
+    for (int p = 0; p < P; ++p) ((uint2*)&ximg2_patch[(buf * P + p) * PATCH + o])[q & 1] = sp[p];
+  };
+
+  // ---- weights: fragment f = half-step * 2 + plane of k-step t (chunk t / 9, tap t % 9) of
+  // this wave's 32 columns, ring slot t % 3
+  const __amdgpu_buffer_rsrc_t rF = rsrc(a.wf + (long long)slot * a.wf_sstride, (long long)a.Ncol * 9 * Cs * 4);
+  const int wbase = ((n0 >> 5) + wn) * NK * 4096 + lane * 16;
+  uint4 wb[3][4];
+  auto gw = [&](int t, int s, int f) __attribute__((always_inline)) {
+    wb[s][f] = __builtin_bit_cast(uint4, bload4(rF, t < NK ? wbase + t * 4096 + f * 1024 : kOOB));
+  };
+
+  f32x16_t acc[MI][1];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
+
+  // patch pixel and patch row of each A fragment row at tap (0, 0) (ximg_kernel's image)
+  int apix[MI], arow[MI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = wm * TM + i * 32 + fr;
+    const int im = m / (W * W), rem = m - im * (W * W);
+    apix[i] = im * PI + (rem / W) * PW + rem % W;
+    arow[i] = rem / W;
+  }
+
+  hs.init(amax_read(a.amax_src, a.amax_src_ld, g), amax_read(a.amax_w, a.amax_w_ld, slot));
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    gw(0, 0, f);
+    gw(1, 1, f);
+  }
+#pragma unroll
+  for (int u = 0; u < NE; ++u) pload1(u, 0);
+#pragma unroll
+  for (int u = 0; u < NE; ++u) {
+    ppiece(u, 0);
+    pload1(u, 1);
+  }
+  __syncthreads();   // patch (chunk 0)
+  for (int c = 0; c < NC; ++c) {
+    const uint4* L = ximg2_patch + (c & 1) * P * PATCH;
+    const bool more = c + 1 < NC;
+    sfor<9>([&](auto TAP) __attribute__((always_inline)) {
+      constexpr int tap = decltype(TAP)::value, ti = tap / 3, tj = tap - ti * 3;
+      constexpr int toff = ti * PW + tj, s = tap % 3, s2 = (tap + 2) % 3;
+      constexpr int u = tap - (9 - NE);           // the patch piece refilled beside this k-step
+      constexpr int NQ = u >= 0 ? 5 : 4;
+      const int t = c * 9 + tap;
+      // no global load and no MFMA crosses a k-step boundary (VALU / SALU / LDS may): left alone,
+      // the scheduler sinks the ring's loads down to their MFMAs, two steps later, and their
+      // latency is exposed
+      __builtin_amdgcn_sched_barrier(0x786);
+      sfor<2>([&](auto KK) __attribute__((always_inline)) {
+        constexpr int kk = decltype(KK)::value;
+        const int ch = kk * 2 + hf;
+        uint4 af[P][MI], bfr[P][1];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const int o = (apix[i] + toff) * CH + (ch ^ ((arow[i] + ti) & 3));
+#pragma unroll
+          for (int p = 0; p < P; ++p) af[p][i] = L[p * PATCH + o];
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) bfr[p][0] = wb[s][kk * 2 + p];
+        mma_half<MI, 1, P, true, NQ, kk>(af, bfr, acc, [&](int q) __attribute__((always_inline)) {
+          if (q < 4) {
+            gw(t + 2, s2, q);   // past NK: zero-filled, never read
+          } else if constexpr (u >= 0) {
+            if (more) ppiece(u, (c + 1) & 1);   // the other buffer: last read before the previous barrier
+            pload1(u, c + 2);
+          }
+        });
+      });
+    });
+    __syncthreads();   // the next chunk's patch is stored; this chunk's reads are done
+  }
+  hs.finish(acc);
+
+  // ---- epilogue from the accumulators: bias, residual, ReLU, max (ximg_kernel's)
+  float* out = a.out + (long long)g * a.out_gstride;
+  const float* bias = a.bias ? a.bias + (long long)slot * a.b_sstride : nullptr;
+  const float* res = a.res ? a.res + (long long)g * a.out_gstride : nullptr;
+  float vmax = 0.f;
+  const int n = n0 + wn * 32 + fr;
+  if (n < a.Ncol) {
+    const float bv = bias ? bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+        if (img0 + m / (W * W) >= nv) continue;
+        const long long o = (long long)(img0 * W * W + m) * a.Ncol + n;
+        float v = acc[i][0][r];
+        if (bias) v += bv;
+        if (res) v += res[o];
+        if (a.relu) v = fmaxf(v, 0.f);
+        vmax = fmaxf(vmax, fabsf(v));
+        out[o] = v;
+      }
+  }
+  if (a.amax_out) amax_fold(a.amax_out, a.amax_out_ld, g, vmax);
+}
+
+// the whole-image halo conv: evaluation forward, 3x3 stride-1 pad-1, square W 8 / 4,
+// Cs % 32 == 0, no fused BN / lazy operands.  dba_ximg_set: 1 (default) ximg2_kernel where the
+// weights carry fragment-ordered planes (ximg_kernel otherwise), 2 ximg_kernel (the bit-equality
+// test's and the kernel bench's A/B), 0 off (the tests' A/B against the implicit GEMM)
 template <int W, int IMGS, int BN, int WM, int WN>
 int ximg_go(const XArgs& a, int G, hipStream_t st) {
   XArgs b = a;
@@ -251,6 +428,27 @@ int ximg_go(const XArgs& a, int G, hipStream_t st) {
   const dim3 grid((unsigned)(ceil_div(a.N, IMGS) * b.tiles_n), G, 1);
   if (a.wp) hipLaunchKernelGGL((ximg_kernel<W, IMGS, BN, WM, WN, true>), grid, dim3(256), 0, st, b);
   else hipLaunchKernelGGL((ximg_kernel<W, IMGS, BN, WM, WN, false>), grid, dim3(256), 0, st, b);
+  DBA_LAUNCH_CHECK();
+}
+// ximg_go's grid; -100: the device refuses the two patch buffers (the caller runs ximg_kernel)
+template <int W, int IMGS, int BN>
+int ximg2_go(const XArgs& a, int G, hipStream_t st) {
+  constexpr int PATCH = IMGS * (W + 2) * (W + 2) * 4;
+  constexpr int LDS = 2 * 2 * PATCH * (int)sizeof(uint4);
+  // the dynamic-LDS attribute is per device (W 4: 73.7 KB, past the 64-KB default)
+  static unsigned long long attr_set = 0ull;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -100;
+  if (!(attr_set >> dev & 1ull)) {
+    if (hipFuncSetAttribute((const void*)ximg2_kernel<W, IMGS, BN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            LDS) != hipSuccess)
+      return -100;
+    attr_set |= 1ull << dev;
+  }
+  XArgs b = a;
+  b.tiles_n = ceil_div(a.Ncol, BN);
+  const dim3 grid((unsigned)(ceil_div(a.N, IMGS) * b.tiles_n), G, 1);
+  hipLaunchKernelGGL((ximg2_kernel<W, IMGS, BN>), grid, dim3(256), LDS, st, b);
   DBA_LAUNCH_CHECK();
 }
 int& ximg_on() {
@@ -267,6 +465,12 @@ int ximg_try(const XArgs& a, int G, int KH, int KW, hipStream_t st) {
   if (!aligned16(a.src) || a.src_gstride % 4 || !aligned16(a.w) || a.w_sstride % 4) return -100;
   if (a.wp && (((uintptr_t)a.wp & 15) || a.wp_sstride % 8)) return -100;
   if (a.sc_src) return -100;   // the fused shortcut: xhalo_kernel only (see ximg_kernel)
+  if (ximg_on() == 1 && a.wp && a.wf && !((uintptr_t)a.wf & 15) && a.wf_sstride % 8 == 0) {
+    int rc = -100;
+    if (a.Wo == 8) rc = a.Ncol >= 128 ? ximg2_go<8, 2, 128>(a, G, st) : ximg2_go<8, 2, 64>(a, G, st);
+    if (a.Wo == 4) rc = a.Ncol >= 128 ? ximg2_go<4, 8, 128>(a, G, st) : ximg2_go<4, 8, 64>(a, G, st);
+    if (rc != -100) return rc;
+  }
   if (a.Wo == 8) return a.Ncol >= 128 ? ximg_go<8, 2, 128, 2, 2>(a, G, st) : ximg_go<8, 2, 64, 2, 2>(a, G, st);
   if (a.Wo == 4) return a.Ncol >= 128 ? ximg_go<4, 8, 128, 2, 2>(a, G, st) : ximg_go<4, 8, 64, 2, 2>(a, G, st);
   return -100;
@@ -318,7 +522,8 @@ DBA_EXPORT int dba_xconv_fwd(const float* x, long long x_gstride, const float* w
                              long long out_gstride, const int* nvalid, int G, int N, int H, int W, int Cin, int Ho,
                              int Wo, int Cout, int KH, int KW, int stride, int pad, int relu, const int* amax_x,
                              int amax_x_ld, const int* amax_w, int amax_w_ld, int* amax_out, int amax_out_ld,
-                             const uint16_t* wp, long long wp_sstride, float* ws, long long ws_floats, int* sk_cnt,
+                             const uint16_t* wp, long long wp_sstride, const uint16_t* wf, long long wf_sstride,
+                             float* ws, long long ws_floats, int* sk_cnt,
                              long long sk_cnt_n, const void* bnf, const float* lz_coef, int lz_relu,
                              void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -333,7 +538,7 @@ DBA_EXPORT int dba_xconv_fwd(const float* x, long long x_gstride, const float* w
   a.sp = stride; a.os = 1; a.dsg = 1; a.relu = relu; a.splitk = 1;
   a.amax_src = amax_x; a.amax_w = amax_w; a.amax_out = amax_out;
   a.amax_src_ld = amax_x_ld; a.amax_w_ld = amax_w_ld; a.amax_out_ld = amax_out_ld;
-  a.wp = wp; a.wp_sstride = wp_sstride;
+  a.wp = wp; a.wp_sstride = wp_sstride; a.wf = wf; a.wf_sstride = wf_sstride;
   a.cls[0] = XClass{KH, KW, -pad, -pad, 0, 0, Ho, Wo, 0};
   if (!amax_x || !amax_w) return -109;   // the fp16 pair needs both operand maxima
   if (bnf) {

@@ -65,7 +65,7 @@ _SIGS = {
     "dba_ximg_set": [_I],
     "dba_xwgrad_halo_set": [_I],
     "dba_xconv_ws_floats": [_I] * 8,
-    "dba_xconv_fwd": [_P, _LL, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 13 + [_P, _I] * 3 + [_P, _LL] * 2
+    "dba_xconv_fwd": [_P, _LL, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 13 + [_P, _I] * 3 + [_P, _LL] * 3
     + [_P, _LL, _P, _P, _I, _P],
     "dba_xconv_sk_ints": [_I] * 8,
     "dba_xconv_dgrad": [_P, _LL, _P, _LL, _P, _P, _P, _LL, _P] + [_I] * 12 + [_P, _I] * 2 + [_P, _LL] * 3 + [_P, _P],
@@ -76,6 +76,7 @@ _SIGS = {
     "dba_xwgrad_stem_ws_floats": [_I] * 6,
     "dba_xsplit_policy": [_I] * 5,
     "dba_xsplit_w_batch": [_P, _I, _I, _P],
+    "dba_xfrag_w_batch": [_P, _I, _I, _P],
     "dba_bn_fold_batch": [_P, _I, _I, _F, _P],
     "dba_xwgrad": [_P, _LL, _P, _LL, _P, _LL, _P] + [_I] * 12 + [_P, _I] * 2 + [_P, _LL, _I] + [_P, _I, _P],
     # fused training BN (csrc/kernels/bnfuse.hpp)
@@ -256,8 +257,10 @@ def _check_w(w: Tensor, dt: torch.dtype = _F32) -> Tuple[Tensor, int]:
 
 
 def set_ximg(on: int) -> int:
-    """Whole-image halo conv of the 8 / 4-wide evaluation stages (xconv_fwd.hip ximg_kernel) on /
-    off; -1 queries.  Returns the previous setting (tests: A/B against the implicit GEMM)."""
+    """Whole-image halo conv of the 8 / 4-wide evaluation stages (xconv_fwd.hip): 1 the
+    fragment-ordered-weight form (ximg2_kernel, the default), 2 the LDS-weight-ring form
+    (ximg_kernel: same bits, the A/B), 0 off (the implicit GEMM); -1 queries.  Returns the
+    previous setting."""
     return int(_L.dba_ximg_set(int(on)))
 
 
@@ -411,6 +414,7 @@ def split_weights(w, sstride: int, per: int, amax):
     out = torch.empty(slots, 2, per, dtype=torch.int16, device=w.device)
     _call("dba_xsplit_w", w.data_ptr(), sstride, per, slots, amax.data_ptr(), amax.shape[1], out.data_ptr(), _stream())
     w._dba_planes = out
+    frag_weights_batch([w])
     return out
 
 
@@ -430,11 +434,41 @@ def split_weights_batch(items) -> None:
     _call("dba_xsplit_w_batch", d.data_ptr(), len(items), slots, _stream())
     for (w, *_), out in zip(items, outs):
         w._dba_planes = out
+    frag_weights_batch([w for w, *_ in items])
+
+
+def frag_weights_batch(ws) -> None:
+    """Fragment-ordered copies of the split planes of the 3x3 weights among ``ws`` ([slots, Cout,
+    3, 3, Cin], Cout and Cin multiples of 32: the shapes the whole-image evaluation conv takes),
+    attached as ``w._dba_fplanes`` ([slots][2 * per] fp16: csrc/kernels/xaux.hip xfrag_w_kernel) in
+    one launch (per 24): the conv's waves load their B fragments from these, 16 bytes per lane.
+    Once per split, like the planes themselves."""
+    desc, outs = [], []
+    for w in ws:
+        p = getattr(w, "_dba_planes", None)
+        if (p is None or w.dim() != 5 or tuple(w.shape[2:4]) != (3, 3) or w.shape[1] % 32 or w.shape[4] % 32
+                or not p.is_contiguous() or p.shape[2] != w[0].numel()):
+            continue
+        out = torch.empty(p.shape[0], 2 * p.shape[2], dtype=torch.int16, device=p.device)
+        desc.append([p.data_ptr(), out.data_ptr(), w.shape[1], w.shape[4], 0])
+        outs.append((w, out))
+    if not desc:
+        return
+    d = torch.tensor(desc, dtype=torch.int64)   # host table, passed by value
+    _call("dba_xfrag_w_batch", d.data_ptr(), len(desc), outs[0][1].shape[0], _stream())
+    for w, out in outs:
+        w._dba_fplanes = out
 
 
 def _wplanes(w):
     """(pointer, slot stride) of ``w``'s fp16-pair planes, if split."""
     p = getattr(w, "_dba_planes", None)
+    return (None, 0) if p is None else (p.data_ptr(), p.stride(0))
+
+
+def _wfplanes(w):
+    """(pointer, slot stride) of ``w``'s fragment-ordered planes (:func:`frag_weights_batch`), if any."""
+    p = getattr(w, "_dba_fplanes", None)
     return (None, 0) if p is None else (p.data_ptr(), p.stride(0))
 
 
@@ -469,7 +503,7 @@ def _xconv_fwd(x, w, wsel, stride, pad, bias, residual, relu, nvalid, out_dtype,
     if out_dtype not in (None, _F32):
         raise TypeError(f"fp32 conv cannot emit {out_dtype} (no silent precision conversion)")
     G, N, H, W, Cin = x.shape
-    attrs = {k: getattr(w, k) for k in ("_dba_amax", "_dba_planes") if hasattr(w, k)}
+    attrs = {k: getattr(w, k) for k in ("_dba_amax", "_dba_planes", "_dba_fplanes") if hasattr(w, k)}
     w, ws = _check_w(w, _F32)
     for k, v in attrs.items():
         setattr(w, k, v)
@@ -524,7 +558,7 @@ def _xconv_fwd(x, w, wsel, stride, pad, bias, residual, relu, nvalid, out_dtype,
     lz_coef, lz_relu = (lz[0].data_ptr(), int(lz[1])) if lz is not None else (None, 0)
     _call("dba_xconv_fwd", x.data_ptr(), N * H * W * Cin, w.data_ptr(), ws, _ptr(_i32(wsel)), _ptr(bias), bs,
           _ptr(res), y.data_ptr(), N * Ho * Wo * Cout, _ptr(_i32(nvalid)), G, N, H, W, Cin, Ho, Wo, Cout, KH, KW,
-          stride, pad, int(relu), *_aptr(ax), *_aptr(aw), *_aptr(ay), *_wplanes(w), _ptr(wsb), n,
+          stride, pad, int(relu), *_aptr(ax), *_aptr(aw), *_aptr(ay), *_wplanes(w), *_wfplanes(w), _ptr(wsb), n,
           _ptr(cnt), 0 if cnt is None else cnt.numel(), bnf_p, lz_coef, lz_relu, _stream())
     return y
 

@@ -221,8 +221,10 @@ def main(argv=None) -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default="", help="substring filter on shape names")
+    ap.add_argument("--ximg", type=int, default=-1, help="hip.set_ximg: 1 ximg2_kernel, 2 ximg_kernel, 0 implicit GEMM")
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
+    H.set_ximg(args.ximg)
     rows = []
     for name, G, N, Hh, Cin, Cout, k, s, p in SHAPES:
         if args.only not in name:
