@@ -13,6 +13,7 @@ Constants mirror reference ``config.py:4-13``.
 from __future__ import annotations
 
 import copy
+import math
 import os
 from typing import Any, Dict, Iterable, List, Optional, Sequence
 
@@ -122,6 +123,11 @@ _DEFAULTS: Dict[str, Any] = {
     "pretrain_central_epochs": 0,  # centralised warm start epochs, before any FedAvg warm start
     "nan_check": True,             # abort the run if the aggregated global model is not finite
     "max_update_norm": None,       # RFA update-norm rejection (helper.py:360-369; never enabled there)
+    # norm-clipped FedAvg (aggregation "mean" only): each client's update is scaled to an L2 norm
+    # of at most C before averaging.  None = off; a finite number > 0 = C; "median" = the lower
+    # median of the round's client update norms.  With diff_privacy the noise then sits on a sum
+    # of bounded sensitivity
+    "clip_norm": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -154,10 +160,18 @@ class Params(dict):
         if self["aggregation_methods"] == AGGR_FOOLSGOLD and self["aggr_epoch_interval"] != 1:
             # reference image_train.py:24 'only works for aggr_epoch_interval=1'
             raise ValueError("foolsgold requires aggr_epoch_interval == 1")
+        if self.clip_norm is not None and self["aggregation_methods"] != AGGR_MEAN:
+            raise ValueError(f"clip_norm is an option of aggregation {AGGR_MEAN!r} "
+                             f"(got {self['aggregation_methods']!r})")
 
     @property
     def type(self) -> str:
         return self["type"]
+
+    @property
+    def clip_norm(self) -> Any:
+        """The checked ``clip_norm``: None (off), the bound C as a float, or ``"median"``."""
+        return check_clip_norm(self.get("clip_norm"))
 
     @property
     def adversary_list(self) -> List[Any]:
@@ -205,6 +219,18 @@ class Params(dict):
 
     def to_plain(self) -> Dict[str, Any]:
         return {k: v for k, v in self.items()}
+
+
+CLIP_MEDIAN = "median"
+
+
+def check_clip_norm(v: Any) -> Any:
+    """None, a finite bound > 0 (returned as float) or ``"median"``; anything else is an error."""
+    if v is None or (isinstance(v, str) and v == CLIP_MEDIAN):
+        return v
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
+        return float(v)
+    raise ValueError(f"clip_norm {v!r}: expected None, a finite number > 0 or {CLIP_MEDIAN!r}")
 
 
 def _same_client(a: Any, b: Any) -> bool:

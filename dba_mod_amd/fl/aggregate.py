@@ -9,6 +9,13 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   the BN running stats too (D2).  The delta sum is an fp64 HIP reduction, per rank then
   all-reduced (``Server._aggregate``).  The int64 ``num_batches_tracked`` counters are not part of the float
   bucket (D1: the reference's float→int64 add crashes on modern torch).
+* :func:`fedavg_clipped` / :func:`clip_factors` — norm-clipped FedAvg (config ``clip_norm``, not in
+  the reference): each client's update is scaled to an L2 norm of at most C (fixed, or the round's
+  lower-median norm) before the average, which bounds what one model-replacement client can
+  move and gives ``diff_privacy``'s noise a sensitivity bound.  Norms and the clipped sum are
+  fused HIP passes over the strided client rows (``ops.delta_stats``,
+  ``ops.clipped_delta_sum_fixed``); the products ``s_i delta_i`` are not exactly summable in
+  fp64, so the sum goes through the same fixed-point limbs as RFA / FoolsGold.
 * :func:`geometric_median` / :func:`geometric_median_distributed` — RFA / Weiszfeld,
   ``helper.py:295-373`` (the latter with the points resident on their owner ranks): one batched distance
   kernel (all n clients in one pass) and one weighted-sum kernel per iteration; weights and
@@ -103,6 +110,52 @@ def fixed_decode(limbs: torch.Tensor, E: int) -> torch.Tensor:
     """fp64 value of [2, L] int64 limb sums on the 2^-(E + 53) grid (elementwise, exact up to the
     final rounding: the same bits for the same limbs)."""
     return limbs[0].double() * (2.0 ** -E) + limbs[1].double() * (2.0 ** -(E + 53))
+
+
+def clip_factors(sqnorms: torch.Tensor, clip) -> Tuple[torch.Tensor, float]:
+    """Per-client clip factors of norm-clipped FedAvg from the squared update norms (fp64 [n]):
+    ``s_i = 1`` if ``norm_i <= C`` else ``C / norm_i`` (a zero-norm client gets 1).  ``clip`` is
+    the bound C, or ``"median"``: the lower median of this round's norms (the sorted fp64 norms
+    at index (n - 1) // 2).  Host fp64 arithmetic on the all-reduced norms, so every rank computes
+    the same factors; the kernels take ``factors.float()``.  Returns (factors fp64 [n] on the
+    host, C).  A NaN norm (a NaN client update) gives a NaN factor, which carries the NaN into the
+    aggregate."""
+    norms = sqnorms.detach().double().cpu().sqrt()
+    n = norms.numel()
+    if isinstance(clip, str):
+        if clip != "median":
+            raise ValueError(f"clip {clip!r}: expected a bound or 'median'")
+        bound = float(torch.sort(norms).values[(n - 1) // 2]) if n else 0.0
+    else:
+        bound = float(clip)
+    factors = torch.where(norms <= bound, torch.ones_like(norms), bound / norms)
+    return factors, bound
+
+
+def clipped_part(rows: torch.Tensor, base: torch.Tensor, scale: torch.Tensor, E: Optional[int]) -> torch.Tensor:
+    """A rank's partial of sum_i scale_i (rows_i - base), fused over the strided rows: [2, L] int64
+    limbs on the 2^E grid, or an fp64 [L] vector when ``E`` is None (shapes of :func:`wsum_part`)."""
+    if E is None:
+        return ops.clipped_delta_sum(rows, base, scale.float())
+    return ops.clipped_delta_sum_fixed(rows, base, scale.float(), E)
+
+
+def fedavg_clipped(global_state: torch.Tensor, finals: torch.Tensor, clip, eta: float, no_models: int,
+                   dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
+    """In-place norm-clipped FedAvg of ``finals`` [n, S] (single rank): ``w += (eta / no_models) *
+    sum_i s_i delta_i (+ noise)`` with the factors of :func:`clip_factors`.  The norm is taken over
+    the ``n_update`` leading entries, exactly the entries aggregated.  The clipped sum goes through
+    the fixed-point limbs (the bits ``Server._aggregate`` reaches from rank partials at any world
+    size); a non-finite update takes the fp64 sum and reaches the model.  Returns (factors, norms)."""
+    rows, base = finals[:, :n_update], global_state[:n_update]
+    n = finals.shape[0]
+    sq, mx = ops.delta_stats(rows, base)
+    factors, _ = clip_factors(sq, clip)
+    E = fixed_exponent(max_abs(mx), n)
+    part = clipped_part(rows, base, factors.to(base.device), E) if n else wsum_zero(n_update, E, base.device)
+    total = part if E is None else fixed_decode(part, E)
+    ops.add_noise_scaled(global_state[:n_update], total, eta / no_models, sigma, seed, dp)
+    return [float(x) for x in factors], [float(x) for x in sq.double().cpu().sqrt()]
 
 
 def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol: float, poll: int = 0):

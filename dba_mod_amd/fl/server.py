@@ -215,8 +215,9 @@ class Server:
         if rounds <= 0:
             return
         p = self.params
-        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr")}
-        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN})
+        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm")}
+        # (plain FedAvg: the warm start stands in for a checkpoint trained without a defence)
+        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None})
         if lr is not None:
             p["lr"] = float(lr)
         try:
@@ -624,7 +625,9 @@ class Server:
         n_upd = self.spec.S if p["aggregate_bn_buffers"] else self.spec.P
         names = [c.name for c in plan.clients]
         dp_seed = (int(p["seed"]) * 7919 + plan.epoch) & 0x7FFFFFFF
-        if method == C.AGGR_MEAN:
+        if method == C.AGGR_MEAN and p.clip_norm is not None:
+            self._aggregate_clipped(plan, local, names, adversarial, p.clip_norm, n_upd, dp_seed)
+        elif method == C.AGGR_MEAN:
             # each rank sums its own clients' deltas (fp64), one all-reduce of S values
             part = ops.delta_sum(local["finals"][:, :n_upd], self.global_state[:n_upd])
             agg.fedavg_apply(self.global_state, self._reduce(part), float(p["eta"]), int(p["no_models"]),
@@ -675,6 +678,43 @@ class Server:
             print("model aggregation took {}s".format(time.time() - t0))
             self.csv.add_weight_result(names, wv.tolist(), alpha.tolist())
             self._plot_weights(names, wv.tolist(), alpha.tolist(), adversarial, plan.epoch)
+
+    def _aggregate_clipped(self, plan: RoundPlan, local: Dict[str, Any], names: List[Any], adversarial: List[Any],
+                           clip: Any, n_upd: int, dp_seed: int) -> None:
+        """Norm-clipped FedAvg (``clip_norm``) on rank-resident clients: every rank takes the norms
+        and max |delta| of its own clients in one fused pass; ONE all-reduce of the [n] fp64
+        squared norms (each row owned by one rank, zero elsewhere: exact) and ONE max-all-reduce
+        of a host float; every rank then computes the same factors and forms its partial clipped
+        sum as fixed-point limbs; ONE all-reduce of the [2, n_upd] int64 limbs (exact, so the
+        global model's bits do not depend on the world size or on which rank holds which client;
+        fp64 partials if an update is not finite: the NaN reaches the model and nan_check aborts)."""
+        p = self.params
+        n = len(plan.clients)
+        idx = local["idx"]
+        rows, base = local["finals"][:, :n_upd], self.global_state[:n_upd]
+        sq = torch.zeros(n, dtype=torch.float64, device=self.device)
+        mx = 0.0
+        if idx:
+            idx_t = torch.tensor(idx, dtype=torch.int64, device=self.device)
+            sq_l, mx_l = ops.delta_stats(rows, base)
+            sq[idx_t] = sq_l
+            mx = agg.max_abs(mx_l)
+        sq = self._reduce(sq)
+        factors, bound = agg.clip_factors(sq, clip)
+        E = agg.fixed_exponent(self._reduce_max(mx), n)
+        if idx:
+            part = agg.clipped_part(rows, base, factors[idx].to(self.device), E)
+        else:
+            part = agg.wsum_zero(n_upd, E, self.device)
+        total = self._reduce(part)
+        ops.add_noise_scaled(base, total if E is None else agg.fixed_decode(total, E),
+                             float(p["eta"]) / int(p["no_models"]), float(p["sigma"]), dp_seed,
+                             bool(p["diff_privacy"]))
+        norms = sq.double().cpu().sqrt()
+        fl, nl = [float(x) for x in factors], [float(x) for x in norms]
+        log.info(f"[clip agg] C: {bound}  clipped: {int((norms > bound).sum())}/{n}  factors: {fl}")
+        self.csv.add_weight_result(names, fl, nl)
+        self._plot_weights(names, fl, nl, adversarial, plan.epoch)
 
     def _log_poison_ratio(self, tag: str, names: List[Any], ns: List[int]) -> None:
         p = self.params

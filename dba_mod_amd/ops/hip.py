@@ -60,6 +60,11 @@ _SIGS = {
     "dba_weighted_sum": [_P, _LL, _P, _I, _P, _LL, _I, _P],
     "dba_weighted_sum_fixed": [_P, _LL, _P, _I, _P, _LL, _D, _P],
     "dba_gram": [_P, _LL, _I, _I, _P, _P, _P],
+    # norm-clipped FedAvg (csrc/kernels/clip.hip)
+    "dba_delta_stats_blocks": [_LL],
+    "dba_delta_stats": [_P, _LL, _I, _P, _LL, _P, _P, _P, _P, _P],
+    "dba_clipped_delta_sum_fixed": [_P, _LL, _I, _P, _P, _P, _LL, _D, _P],
+    "dba_clipped_delta_sum": [_P, _LL, _I, _P, _P, _P, _LL, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
@@ -1289,6 +1294,67 @@ def weighted_sum_fixed(points, wts, E):
     out = torch.empty(2, L, dtype=torch.int64, device=points.device)
     _call("dba_weighted_sum_fixed", points.data_ptr(), points.stride(0), wts.float().contiguous().data_ptr(), n,
           out.data_ptr(), L, float(2.0 ** E), _stream())
+    return out
+
+
+def _delta_rows(rows, base):
+    """(rows, row stride, base) of the clip kernels: fp32 strided rows [n, L] against base [L]."""
+    assert rows.dtype == torch.float32 and base.dtype == torch.float32
+    assert rows.dim() == 2 and rows.shape[1] == base.numel(), (tuple(rows.shape), base.numel())
+    assert base.is_cuda and rows.device == base.device
+    if rows.shape[1] > 1 and rows.stride(1) != 1:
+        rows = rows.contiguous()
+    return rows, (rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), base.contiguous()
+
+
+def _clip_scale(scale, n, device):
+    """The [n] fp32 clip factors on the rows' device."""
+    assert scale.numel() == n
+    return scale.to(device=device, dtype=torch.float32).contiguous()
+
+
+def delta_stats(rows, base):
+    """(||rows_i - base||^2 fp64 [n], max |rows_i - base| fp32 [n], NaN -> +inf) in one pass over
+    the strided rows (clip.hip delta_stats_kernel): bitwise run to run."""
+    rows, rs, base = _delta_rows(rows, base)
+    n, L = rows.shape
+    if n == 0 or L == 0:
+        return (torch.zeros(n, dtype=torch.float64, device=base.device),
+                torch.zeros(n, dtype=torch.float32, device=base.device))
+    sq = torch.empty(n, dtype=torch.float64, device=base.device)
+    mx = torch.empty(n, dtype=torch.float32, device=base.device)
+    nb = int(_L.dba_delta_stats_blocks(L))
+    part_sq = torch.empty(n * nb, dtype=torch.float64, device=base.device)
+    part_mx = torch.empty(n * nb, dtype=torch.float32, device=base.device)
+    _call("dba_delta_stats", rows.data_ptr(), rs, n, base.data_ptr(), L, sq.data_ptr(), mx.data_ptr(),
+          part_sq.data_ptr(), part_mx.data_ptr(), _stream())
+    return sq, mx
+
+
+def clipped_delta_sum_fixed(rows, base, scale, E):
+    """[2, L] int64 fixed-point limb sums of sum_i scale[i] * (rows[i] - base) at scale 2^E (clip.hip
+    clipped_sum_kernel): order-free, so rank partials all-reduce to world-invariant bits."""
+    rows, rs, base = _delta_rows(rows, base)
+    n, L = rows.shape
+    if n == 0 or L == 0:
+        return torch.zeros(2, L, dtype=torch.int64, device=base.device)
+    scale = _clip_scale(scale, n, base.device)
+    out = torch.empty(2, L, dtype=torch.int64, device=base.device)
+    _call("dba_clipped_delta_sum_fixed", rows.data_ptr(), rs, n, base.data_ptr(), scale.data_ptr(), out.data_ptr(),
+          L, float(2.0 ** E), _stream())
+    return out
+
+
+def clipped_delta_sum(rows, base, scale):
+    """fp64 [L] sum_i scale[i] * (rows[i] - base), in row order (the fallback off the fixed grid)."""
+    rows, rs, base = _delta_rows(rows, base)
+    n, L = rows.shape
+    if n == 0 or L == 0:
+        return torch.zeros(L, dtype=torch.float64, device=base.device)
+    scale = _clip_scale(scale, n, base.device)
+    out = torch.empty(L, dtype=torch.float64, device=base.device)
+    _call("dba_clipped_delta_sum", rows.data_ptr(), rs, n, base.data_ptr(), scale.data_ptr(), out.data_ptr(), L,
+          _stream())
     return out
 
 

@@ -560,6 +560,51 @@ def weighted_sum_fixed(points: Tensor, wts: Tensor, E: int) -> Tensor:
     return torch.stack([hi.to(torch.int64).sum(0), lo.to(torch.int64).sum(0)])
 
 
+def delta_stats(rows: Tensor, base: Tensor) -> Tuple[Tensor, Tensor]:
+    """(||rows_i - base||^2 in fp64 [n], max |rows_i - base| in fp32 [n]) of the client updates,
+    without keeping the [n, L] deltas (clip.hip delta_stats_kernel is the GPU form).  The delta is
+    the fp64 difference; the max is taken over its fp32 rounding, a NaN mapped to +inf (so no
+    later max can swallow it); a NaN delta makes its client's squared norm NaN.  Each row is
+    summed on its own, so a client's bits do not depend on which other rows share the call."""
+    n = rows.shape[0]
+    sq = torch.zeros(n, dtype=torch.float64, device=base.device)
+    mx = torch.zeros(n, dtype=torch.float32, device=base.device)
+    if base.numel() == 0:
+        return sq, mx
+    b = base.double()
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=base.device)
+    for i in range(n):
+        d = rows[i].double() - b
+        sq[i] = (d * d).sum()
+        a = d.float().abs()
+        mx[i] = torch.where(a.isnan(), inf, a).max()
+    return sq, mx
+
+
+def clipped_delta_sum_fixed(rows: Tensor, base: Tensor, scale: Tensor, E: int) -> Tensor:
+    """[2, L] int64 limb sums of sum_i scale[i] * (rows[i] - base) on the fixed grid 2^-(E + 53):
+    q = scale * (rows - base) * 2^E evaluated in fp64 in exactly this order, hi = floor(q), lo =
+    floor((q - hi) 2^53), each product quantised on its own, then summed exactly (order-free;
+    clip.hip clipped_sum_kernel computes the same limbs bit for bit)."""
+    L = base.numel()
+    if rows.shape[0] == 0:
+        return torch.zeros(2, L, dtype=torch.int64, device=base.device)
+    d = rows.double() - base.double()[None]
+    q = (scale.float().double()[:, None] * d) * (2.0 ** E)
+    hi = torch.floor(q)
+    lo = torch.floor((q - hi) * 2.0 ** 53)
+    return torch.stack([hi.to(torch.int64).sum(0), lo.to(torch.int64).sum(0)])
+
+
+def clipped_delta_sum(rows: Tensor, base: Tensor, scale: Tensor) -> Tensor:
+    """fp64 [L] sum_i scale[i] * (rows[i] - base): the clipped sum off the fixed grid (a NaN / Inf
+    delta is carried into it)."""
+    L = base.numel()
+    if rows.shape[0] == 0:
+        return torch.zeros(L, dtype=torch.float64, device=base.device)
+    return (scale.float().double()[:, None] * (rows.double() - base.double()[None])).sum(0)
+
+
 def gram(feats: Tensor) -> Tensor:
     """F F^T in float64 (K15)."""
     f = feats.double()

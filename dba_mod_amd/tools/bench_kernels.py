@@ -216,6 +216,44 @@ def _bench_xent(name, G, B, C, reps, dev):
             "r5_eval_us": round(t_eval5 * 1e6, 2)}
 
 
+# norm-clipped FedAvg (clip.hip): n clients x S floats — a CIFAR round's 10 final states of the
+# half-width ResNet-18 (S = 2,802,430; the rows are the [:, :S] view of the stacked states)
+CLIP = [("clip.cifar", 10, 2_802_430)]
+
+
+def _bench_clip(name, n, S, reps, dev):
+    """The two fused passes against the composed path they replace: torch ``finals - global``
+    materialised as [n, S], then sq_dists and weighted_sum_fixed over it.  GB/s counts the bytes
+    each form must move (rows + base in; norms, or the [2, S] int64 limbs, out)."""
+    from dba_mod_amd.fl import aggregate as agg
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    finals = base[None] + 0.01 * torch.randn(n, S, device=dev)
+    finals[0] = base + 100.0 * (finals[0] - base)                 # a model-replacement client
+    zero = torch.zeros(S, device=dev)
+    sq, mx = H.delta_stats(finals, base)
+    factors, _ = agg.clip_factors(sq, "median")
+    scale = factors.float().to(dev)
+    E = agg.fixed_exponent(agg.max_abs(mx), n)
+    t_stats = _time(lambda: H.delta_stats(finals, base), reps)
+    t_sum = _time(lambda: H.clipped_delta_sum_fixed(finals, base, scale, E), reps)
+    t_sum64 = _time(lambda: H.clipped_delta_sum(finals, base, scale), reps)
+    t_delta = _time(lambda: finals - base[None], reps)
+    delta = finals - base[None]
+    t_sqd = _time(lambda: H.sq_dists(delta, zero), reps)
+    t_wsum = _time(lambda: H.weighted_sum_fixed(delta, scale, E), reps)
+    b_in = (n + 1) * S * 4
+    return {"shape": name, "n": n, "S": S, "delta_stats_us": round(t_stats * 1e6, 1),
+            "delta_stats_GBps": round(b_in / t_stats / 1e9, 1),
+            "clipped_sum_fixed_us": round(t_sum * 1e6, 1),
+            "clipped_sum_fixed_GBps": round((b_in + 2 * S * 8) / t_sum / 1e9, 1),
+            "clipped_sum_f64_us": round(t_sum64 * 1e6, 1),
+            "fused_us": round((t_stats + t_sum) * 1e6, 1),
+            "composed_delta_us": round(t_delta * 1e6, 1), "composed_sq_dists_us": round(t_sqd * 1e6, 1),
+            "composed_wsum_fixed_us": round(t_wsum * 1e6, 1),
+            "composed_us": round((t_delta + t_sqd + t_wsum) * 1e6, 1)}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -238,6 +276,10 @@ def main(argv=None) -> int:
     for name, G, B, C in XENT:
         if args.only in name:
             rows.append(_bench_xent(name, G, B, C, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, n, S in CLIP:
+        if args.only in name:
+            rows.append(_bench_clip(name, n, S, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
