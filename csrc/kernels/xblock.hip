@@ -58,6 +58,8 @@ struct XBArgs {
   const uint16_t* w0p; long long w0_sstride;
   const float* b0; long long b0_sstride;
   const int* amax_w0;
+  // GL only: w1p / w2p in fragment order per slot (xaux.hip xfrag_w_kernel), wf_sstride apart
+  const uint16_t* w1f; const uint16_t* w2f; long long wf_sstride;
 };
 
 constexpr int kW = 32, kC = 32, kTR = 8;      // image width, channels, output rows per block
@@ -73,13 +75,44 @@ constexpr int kCi = 3, kK0 = 9 * kCi;        // STEM: image channels, stem reduc
 constexpr int kIR = kPR + 2, kIW = kW + 2;   // STEM: image rows h0-3 .. h0+10, cols -1 .. 32
 constexpr int kIm = kIR * kIW * kCi;         // STEM: image patch floats
 static_assert(kPR * kW * kC * 4 <= 2 * kPatch * 16, "fp32 staging of the stem / mid rows fits the patch");
+constexpr int kStage = 3 * 4 * 64;           // GL: uint4 per weight stage (a tap row: 3 k-steps x 4 pieces of 1 KB)
+constexpr int kStages = 6;                   // GL: 3 tap rows of conv1, then 3 of conv2
+static_assert(kIm * 4 <= kStage * 16, "the stem's image fits a weight stage buffer");
 
-template <bool STEM>
+// GL (dba_xstage_set): the weights come fragment-ordered (XBArgs::w1f / w2f), where the B fragments
+// of one k-step, half-step and plane are one 1-KB block with lane l's 16 bytes at 16 l — the
+// lane-linear image an LDS-DMA load (global_load_lds_dwordx4) writes.  A weight stage is a whole
+// tap row (3 k-steps = 12 such pieces, contiguous in the planes: 12 KB), two stages in LDS; each
+// wave copies 3 pieces of the next stage right after the barrier that frees its buffer, so the
+// copy is in flight for a whole stage (36 - 54 MFMAs per wave) with no VGPR, no ds_write and no
+// swizzle arithmetic, waits for its own pieces at the end of the stage and meets the others at
+// ONE barrier per tap row instead of one per tap.  B fragments are ds_read_b128s at constant
+// offsets off 16 * lane (conflict-free); the taps of a stage are unrolled at compile time.  Same
+// k order, MFMA order and operands per output element as the ring form: the same bits.
+// The LDS-DMA load is not bounds-checked (the ring form's buffer loads are): the launchers take
+// this form only for fragment planes that hold a whole 32 x 288 weight per slot.
+template <bool STEM, bool GL>
 __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
-  __shared__ __attribute__((aligned(16))) uint4 patch[2 * kPatch];
-  __shared__ __attribute__((aligned(16))) uint4 bring[2 * 2 * kBPL];
-  __shared__ float red[3][4];                // block maxima: image (STEM), stem output (STEM), mid
-  __shared__ float im[STEM ? kIm : 1];
+  // GL: one LDS object (patch | two weight stages | maxima: 76.9 KB, two blocks per CU); the stem's
+  // image lies in stage buffer 1, whose first fill is issued after the stem's last read of it and
+  // a barrier
+  __shared__ __attribute__((aligned(16))) uint4 patch_s[2 * kPatch + (GL ? 2 * kStage + 3 : 0)];
+  __shared__ __attribute__((aligned(16))) uint4 bring_s[GL ? 1 : 2 * 2 * kBPL];
+  __shared__ float red_s[GL ? 1 : 3][4];     // block maxima: image (STEM), stem output (STEM), mid
+  __shared__ float im_s[STEM && !GL ? kIm : 1];
+  uint4* const patch = patch_s;
+  uint4* bring;
+  float (*red)[4];
+  float* im;
+  if constexpr (GL) {
+    bring = patch_s + 2 * kPatch;
+    red = reinterpret_cast<float (*)[4]>(patch_s + 2 * kPatch + 2 * kStage);
+    im = reinterpret_cast<float*>(patch_s + 2 * kPatch + kStage);
+  } else {
+    bring = bring_s;
+    red = red_s;
+    im = im_s;
+  }
 
   const int g = blockIdx.y;
   const int img = blockIdx.x / (kW / kTR), h0 = (blockIdx.x % (kW / kTR)) * kTR;
@@ -91,6 +124,41 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
   const float* __restrict__ src = a.x + (long long)g * a.x_gstride + (long long)img * kW * kW * (STEM ? kCi : kC);
   constexpr int Q4 = kC / 4;                       // float4 per pixel
   float* Ct = reinterpret_cast<float*>(patch);     // fp32 staging of whole rows (stem, mid, output)
+
+  // conv1's 10 row tiles over 4 waves: rows wid and wid + 4, and two waves take a third (rows 8,
+  // 9).  Ring form: waves 0, 1.  GL: waves 2, 3 in every other group of 8 blocks (the blocks of
+  // one group go to the 8 XCDs, so a CU's two resident blocks differ in blockIdx.x >> 3 as often
+  // as not and their heavy waves then sit on different SIMDs) — ownership only, the same tiles
+  const int row2 = GL ? 8 + (wid & 1) : wid + 8;
+  const bool heavy = GL ? (wid >> 1) == (int)((blockIdx.x >> 3) & 1) : wid < 2;
+
+  // GL: stage s (< 3: conv1's tap row s, then conv2's tap row s - 3) into stage buffer s & 1;
+  // this wave's 3 pieces, 16 B per lane
+  auto fill = [&](int s) __attribute__((always_inline)) {
+    const uint16_t* F = (s < 3 ? a.w1f : a.w2f) + (long long)slot * a.wf_sstride + (s < 3 ? s : s - 3) * (kStage * 8) +
+                        wid * (3 * 512) + lane * 8;
+    // (inline asm, not __builtin_amdgcn_global_load_lds: with the builtin the compiler drains
+    // vmcnt(0) before the next LDS read of ANY address, the patch's included, which puts the whole
+    // copy's latency in front of the stage it should hide behind.  The destination is M0 (the
+    // wave-uniform LDS byte address) + 16 * lane; M0 is written and restored in the statement.)
+    const uint32_t dst = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(bring + (s & 1) * kStage + wid * (3 * 64)));
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(F + j * 512), "s"(dst + j * 1024)
+                   : "memory");
+    }
+  };
+  // this wave's pieces have landed (the compiler does not count them), then everyone's; the
+  // buffer read last is free
+  auto gl_sync = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+  if constexpr (GL) fill(0);
 
   // fp32 rows [0, NR) staged in Ct (zeros on rows outside the image) -> the patch layout split
   // with this block's max (``red``: the waves' maxima), zero padding columns; returns the scale
@@ -324,13 +392,57 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
     __syncthreads();
   };
 
-  gq(0, 0);
-  gq(1, 1);
-  lput(0, 0);
-  gq(2, 0);
-  __syncthreads();   // patch + conv1's first weight step
+  // GL: one weight stage: the wave's MI row tiles at the 3 taps of row ti, B from stage buffer buf
+  auto stage = [&](auto MIc, int ti, int buf) __attribute__((always_inline)) {
+    constexpr int MI = decltype(MIc)::value;
+    const uint4* L = bring + buf * kStage + lane;
+    f32x16_t (&ac)[MI][1] = *reinterpret_cast<f32x16_t (*)[MI][1]>(&acc[0]);
+    // the fragments of half-step h (tap column h / 2, half h % 2) -> set h & 1
+    uint4 af[2][2][MI], bfr[2][2][1];
+    auto frags = [&](auto Hc) __attribute__((always_inline)) {
+      constexpr int h = decltype(Hc)::value, tj = h / 2, kk = h % 2, st = h & 1;
+      const int ch = kk * 2 + hf;
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int pp = ((i < 2 ? wid + 4 * i : row2) + ti) * kPW + fr + tj;
+        const int o = pp * kCH + (ch ^ hswz<kW, kC>(pp, 0));
+        af[st][0][i] = patch[o];
+        af[st][1][i] = patch[kPatch + o];
+      }
+      bfr[st][0][0] = L[(tj * 4 + kk * 2) * 64];
+      bfr[st][1][0] = L[(tj * 4 + kk * 2 + 1) * 64];
+    };
+    // the next half-step's fragment reads are written ahead of this one's MFMAs, with a
+    // scheduling fence behind the MFMAs: the scheduler then issues them beside the half-step's
+    // last MFMAs.  Measured on the block row (17 x 1024 images, parent 2659 us): no fence (each
+    // read sunk to just before its MFMA) 2631, this 2610, a second fence that pins all the reads
+    // ahead of the MFMAs 2652 us (profiles/r8/xstage/README.md)
+    frags(std::integral_constant<int, 0>{});
+    sfor<6>([&](auto Hc) __attribute__((always_inline)) {
+      constexpr int h = decltype(Hc)::value;
+      if constexpr (h + 1 < 6) frags(std::integral_constant<int, h + 1>{});
+      mma_half<MI, 1, 2, true, 0, h % 2>(af[h & 1], bfr[h & 1], ac, [](int) {});
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
 
-  for (int t = 0; t < 9; ++t) run(t);
+  if constexpr (GL) {
+    gl_sync();   // patch + conv1's first stage
+    for (int s = 0; s < 3; ++s) {
+      fill(s + 1);   // (s = 2: conv2's first stage, landed before the mid activation is resplit)
+      if (heavy) stage(std::integral_constant<int, 3>{}, s, s & 1);
+      else stage(std::integral_constant<int, 2>{}, s, s & 1);
+      gl_sync();
+    }
+  } else {
+    gq(0, 0);
+    gq(1, 1);
+    lput(0, 0);
+    gq(2, 0);
+    __syncthreads();   // patch + conv1's first weight step
+
+    for (int t = 0; t < 9; ++t) run(t);
+  }
 
   // ---- mid activation: h = relu(conv1 + b1), zero on rows outside the image; staged in fp32
   // through the (dead) patch memory, then re-split with this block's scale into the patch layout
@@ -340,8 +452,8 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
   float vmax = 0.f;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const int mr = wid + 4 * i;
-    if (mr >= kMR) break;   // waves 2, 3 own two tiles
+    if (i == 2 && !heavy) break;   // two waves own two tiles
+    const int mr = i < 2 ? wid + 4 * i : row2;
     const bool in_img = (unsigned)(h0 - 1 + mr) < (unsigned)kW;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -360,7 +472,15 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
   zero();
   __syncthreads();
 
-  for (int t = 9; t < kSteps; ++t) run(t);
+  if constexpr (GL) {
+    for (int s = 3; s < kStages; ++s) {
+      if (s + 1 < kStages) fill(s + 1);
+      stage(std::integral_constant<int, 2>{}, s - 3, s & 1);
+      gl_sync();
+    }
+  } else {
+    for (int t = 9; t < kSteps; ++t) run(t);
+  }
 
   // ---- output: y = relu(conv2 + b2 + x), fp32, through LDS for row-contiguous stores
   hs.finish(*reinterpret_cast<f32x16_t (*)[2][1]>(&acc[0]));
@@ -397,13 +517,28 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
   if (a.amax_out) amax_fold(a.amax_out, a.amax_out_ld, g, omax);
 }
 
+// which variants take the staged form (GL) under dba_xstage_set(1) (each where its kernel-bench
+// row beat the parent's by more than three times the parent's run-to-run spread:
+// profiles/r8/xstage/README.md)
+constexpr bool kXStageBlockDefault = true, kXStageStemDefault = false;
+// the staged form takes the block: selected (dba_xstage_set, xconv_fwd.hip), and both convs carry
+// whole fragment-ordered planes (its LDS-DMA loads are not bounds-checked: 16-B aligned, 32 x 288
+// elements x 2 planes inside every slot's stride)
+bool xstage_ok(bool dflt, const uint16_t* w1f, const uint16_t* w2f, long long wf_sstride) {
+  const int mode = xg::xstage_mode();
+  return (mode == 3 || (mode == 1 && dflt)) && w1f && w2f && !((uintptr_t)w1f & 15) && !((uintptr_t)w2f & 15) &&
+         wf_sstride % 8 == 0 && wf_sstride >= 2 * kC * kK;
+}
+
 }  // namespace
 
 // y = relu(conv2(relu(conv1(x) + b1)) + b2 + x) for [G][N][32][32][32] fp32 activations with
 // pre-split fp16-pair weights (both convs [slots][32][3][3][32], planes wp_sstride apart per
-// slot).  Returns -100 for any other shape (the caller runs the two convs).
+// slot; w1f / w2f: the same planes fragment-ordered, wf_sstride apart, or null).  Returns -100
+// for any other shape (the caller runs the two convs).
 DBA_EXPORT int dba_xblock_fwd(const float* x, long long x_gstride, float* out, long long out_gstride, const int* wsel,
-                              const uint16_t* w1p, const uint16_t* w2p, long long wp_sstride, const float* b1,
+                              const uint16_t* w1p, const uint16_t* w2p, long long wp_sstride, const uint16_t* w1f,
+                              const uint16_t* w2f, long long wf_sstride, const float* b1,
                               const float* b2, long long b_sstride, const int* nvalid, int G, int N, int H, int W,
                               int C, int Cout, const int* amax_x, int amax_x_ld, const int* amax_w1,
                               const int* amax_w2, int amax_w_ld, int* amax_out, int amax_out_ld, void* stream) {
@@ -415,19 +550,25 @@ DBA_EXPORT int dba_xblock_fwd(const float* x, long long x_gstride, float* out, l
   if ((long long)N * H * W * C >= (1LL << 29)) return -103;
   XBArgs a{x, x_gstride, out, out_gstride, wsel, w1p, w2p, wp_sstride, b1, b2, b_sstride, nvalid, N,
            amax_x, amax_x_ld, amax_w1, amax_w2, amax_w_ld, amax_out, amax_out_ld,
-           nullptr, 0, nullptr, 0, nullptr};
-  hipLaunchKernelGGL(xblock_kernel<false>, dim3((unsigned)(N * (kW / kTR)), G), dim3(256), 0, (hipStream_t)stream, a);
+           nullptr, 0, nullptr, 0, nullptr, w1f, w2f, wf_sstride};
+  const dim3 grid((unsigned)(N * (kW / kTR)), G);
+  if (xstage_ok(kXStageBlockDefault, w1f, w2f, wf_sstride))
+    hipLaunchKernelGGL((xblock_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((xblock_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
   DBA_LAUNCH_CHECK();
 }
 
 // The stem + the first identity BasicBlock of the 32-wide stage:
 //   x = relu(stem(img) + b0),  y = relu(conv2(relu(conv1(x) + b1)) + b2 + x)
 // for [G][N][32][32][3] fp32 images (stem [slots][32][3][3][3], pre-split planes [2][32 * 27]
-// w0_sstride apart per slot; conv1 / conv2 as dba_xblock_fwd).  -100 for any other shape.
+// w0_sstride apart per slot; conv1 / conv2 and their weight path as dba_xblock_fwd).  -100 for
+// any other shape.
 DBA_EXPORT int dba_xblock_stem_fwd(const float* img, long long img_gstride, float* out, long long out_gstride,
                                    const int* wsel, const uint16_t* w0p, long long w0_sstride, const float* b0,
                                    long long b0_sstride, const uint16_t* w1p, const uint16_t* w2p,
-                                   long long wp_sstride, const float* b1, const float* b2, long long b_sstride,
+                                   long long wp_sstride, const uint16_t* w1f, const uint16_t* w2f,
+                                   long long wf_sstride, const float* b1, const float* b2, long long b_sstride,
                                    const int* nvalid, int G, int N, int H, int W, int Cin, int C,
                                    const int* amax_w0, const int* amax_w1, const int* amax_w2, int amax_w_ld,
                                    int* amax_out, int amax_out_ld, void* stream) {
@@ -440,7 +581,11 @@ DBA_EXPORT int dba_xblock_stem_fwd(const float* img, long long img_gstride, floa
   if ((long long)N * H * W * C >= (1LL << 29)) return -103;
   XBArgs a{img, img_gstride, out, out_gstride, wsel, w1p, w2p, wp_sstride, b1, b2, b_sstride, nvalid, N,
            nullptr, 0, amax_w1, amax_w2, amax_w_ld, amax_out, amax_out_ld,
-           w0p, w0_sstride, b0, b0_sstride, amax_w0};
-  hipLaunchKernelGGL(xblock_kernel<true>, dim3((unsigned)(N * (kW / kTR)), G), dim3(256), 0, (hipStream_t)stream, a);
+           w0p, w0_sstride, b0, b0_sstride, amax_w0, w1f, w2f, wf_sstride};
+  const dim3 grid((unsigned)(N * (kW / kTR)), G);
+  if (xstage_ok(kXStageStemDefault, w1f, w2f, wf_sstride))
+    hipLaunchKernelGGL((xblock_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((xblock_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
   DBA_LAUNCH_CHECK();
 }

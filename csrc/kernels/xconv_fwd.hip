@@ -10,6 +10,10 @@ SplitPolicy& split_policy() {
   static SplitPolicy p;
   return p;
 }
+int& xstage_mode() {
+  static int mode = 1;
+  return mode;
+}
 }  // namespace xg
 
 namespace {
@@ -451,6 +455,202 @@ int ximg2_go(const XArgs& a, int G, hipStream_t st) {
   hipLaunchKernelGGL((ximg2_kernel<W, IMGS, BN>), grid, dim3(256), LDS, st, b);
   DBA_LAUNCH_CHECK();
 }
+// ================================================================ 16-wide halo conv, staged weights
+// xhalo_kernel<16, 64, 128, 64, 2, 2, PRE> (xhalo.hpp: the evaluation forward of the 16-wide
+// stage's plain 64 -> 64 3x3 convs) with the weight path of xblock.hip's GL form: tile, patch, k
+// order (tap, then channel block), MFMA sequence per output element and epilogue are that
+// kernel's — the same bits — but the B fragments come from the fragment-ordered planes
+// (XArgs::wf: k-step index = channel block * 9 + tap) by LDS-DMA.  A weight stage is one tap: its
+// two 32-channel k-steps for both 32-column tiles = 16 pieces of 1 KB; wave w copies the 4
+// pieces of (column tile w / 2, channel block w % 2), 4 KB contiguous in the planes.  Two stages
+// in LDS: 9 barriers instead of 18, the copy in flight for a whole stage (24 MFMAs per wave), no
+// VGPR, ds_write or swizzle arithmetic on the weight path, B fragment reads at constant offsets
+// off 16 * lane.
+// LDS 46,080 (patch) + 32,768 + 1,024 B: two blocks per CU.  The LDS-DMA loads are not
+// bounds-checked: xstage16_try admits only whole 64 x 576 fragment planes.
+__global__ __launch_bounds__(256) void xstage16_kernel(const XArgs a) {
+  constexpr int P = 2, W = 16, CS = 64, BM = 128, BN = 64, WN = 2;
+  constexpr int TR = BM / W, PW = W + 2, PR = TR + 2, PP = PR * PW;
+  constexpr int CH = CS / 8, PATCH = PP * CH;             // uint4 per plane
+  constexpr int TM = 64, TN = 32, MI = TM / 32;
+  constexpr int CB = CS / 32;                             // channel blocks (k-steps) per tap
+  constexpr int STG = (BN / 32) * CB * 4 * 64;            // uint4 per stage
+  static_assert(BM * BN <= P * PATCH * 4, "epilogue tile fits the patch");
+  __shared__ __attribute__((aligned(16))) uint4 lds[P * PATCH + 2 * STG];   // patch | two weight stages
+  __shared__ long long orow[BM];
+  uint4* const patch = lds;
+  uint4* const bring = lds + P * PATCH;
+
+  const int g = blockIdx.y;
+  const int HT = a.Ho / TR;                               // row tiles per image
+  const int tm = blockIdx.x;
+  const int img = tm / HT, h0 = (tm - img * HT) * TR;
+  if (img >= valid_rows(a.nvalid, g, a.N)) return;
+  const int slot = a.wsel ? a.wsel[g] : g;
+  const float* __restrict__ src = a.src + (long long)g * a.src_gstride;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+  const int fr = lane & 31, hf = lane >> 5;
+
+  // tap's stage into stage buffer tap & 1: this wave's 4 pieces, 16 B per lane (inline asm: see
+  // xblock.hip's fill; the destination is M0 + 16 * lane)
+  const uint16_t* F = a.wf + (long long)slot * a.wf_sstride + ((wid >> 1) * (CB * 9) + (wid & 1) * 9) * 2048 + lane * 8;
+  auto fill = [&](int tap) __attribute__((always_inline)) {
+    const uint32_t dst = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(bring + (tap & 1) * STG + wid * 256));
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(F + tap * 2048 + f * 512), "s"(dst + f * 1024)
+                   : "memory");
+    }
+  };
+  auto gl_sync = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+  fill(0);
+
+  if (tid < BM)
+    orow[tid] = (((long long)img * a.Ho + h0 + tid / W) * a.Wo + tid % W) * a.Ncol;
+
+  // ---- the input patch (xhalo_kernel's): rows h0-1 .. h0+TR, cols -1 .. W, split once
+  constexpr int Q4 = CS / 4;
+  constexpr int NE = (PP * Q4 + 255) / 256;
+  float4 pv[NE];
+  {
+    const __amdgpu_buffer_rsrc_t rA = rsrc(src, (long long)a.N * a.Hs * a.Ws * CS * 4);
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+      const int e = tid + 256 * u;
+      const int pp = e / Q4, q = e - pp * Q4;
+      const int pr = pp / PW, pc = pp - pr * PW;
+      const int h = h0 - 1 + pr, w = pc - 1;
+      const bool ok = e < PP * Q4 && (unsigned)h < (unsigned)a.Hs && (unsigned)w < (unsigned)a.Ws;
+      pv[u] = bload4(rA, ok ? (((img * a.Hs + h) * a.Ws + w) * CS + q * 4) * 4 : kOOB);
+    }
+  }
+  HScale hs;
+  hs.init(amax_read(a.amax_src, a.amax_src_ld, g), amax_read(a.amax_w, a.amax_w_ld, slot));
+#pragma unroll
+  for (int u = 0; u < NE; ++u) {
+    const int e = tid + 256 * u;
+    if (e >= PP * Q4) break;
+    const int pp = e / Q4, q = e - pp * Q4;
+    uint2 sp[P];
+    split4h(pv[u].x, pv[u].y, pv[u].z, pv[u].w, hs.ma, sp);
+    const int o = pp * CH + ((q >> 1) ^ hswz<W, CS>(pp, pp % PW));
+#pragma unroll
+    for (int p = 0; p < P; ++p) ((uint2*)&patch[p * PATCH + o])[q & 1] = sp[p];
+  }
+
+  f32x16_t acc[MI][1];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
+  int apix[MI], acol[MI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = wm * TM + i * 32 + fr;
+    apix[i] = (m / W) * PW + (m % W);
+    acol[i] = m % W;
+  }
+
+  // one tap: half-steps h = channel block * 2 + half, fragment set h & 1
+  auto stage = [&](int tap) __attribute__((always_inline)) {
+    const int ti = tap / 3, tj = tap - ti * 3;
+    const int toff = ti * PW + tj;
+    const uint4* L = bring + (tap & 1) * STG + wn * (CB * 4 * 64) + lane;
+    uint4 af[2][P][MI], bfr[2][P][1];
+    auto frags = [&](auto Hc) __attribute__((always_inline)) {
+      constexpr int h = decltype(Hc)::value, cb = h / 2, kk = h % 2, st = h & 1;
+      const int ch = kk * 2 + hf;
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int pp = apix[i] + toff;
+        const int o = pp * CH + ((cb * 4 + ch) ^ hswz<W, CS>(pp, acol[i] + tj));
+#pragma unroll
+        for (int p = 0; p < P; ++p) af[st][p][i] = patch[p * PATCH + o];
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) bfr[st][p][0] = L[(cb * 4 + kk * 2 + p) * 64];
+    };
+    // the next half-step's fragment reads are pinned ahead of this one's MFMAs (left alone, the
+    // scheduler sinks each read to just before its MFMA).  eval.layer2, 17 x 1024 images, parent
+    // 1153 us: reads sunk 1087, fence behind the MFMAs only 1087, this 1083 us
+    // (profiles/r8/xstage/README.md)
+    frags(std::integral_constant<int, 0>{});
+    sfor<2 * CB>([&](auto Hc) __attribute__((always_inline)) {
+      constexpr int h = decltype(Hc)::value;
+      if constexpr (h + 1 < 2 * CB) frags(std::integral_constant<int, h + 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+      mma_half<MI, 1, P, true, 0, h % 2>(af[h & 1], bfr[h & 1], acc, [](int) {});
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+
+  gl_sync();   // patch + the first stage
+  for (int tap = 0; tap < 9; ++tap) {
+    if (tap + 1 < 9) fill(tap + 1);   // its buffer's last reads ended before the barrier just passed
+    stage(tap);
+    gl_sync();
+  }
+  hs.finish(acc);
+
+  // ---- epilogue through the (drained) patch memory (xhalo_kernel's)
+  float* Ct = reinterpret_cast<float*>(patch);
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      Ct[(wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf) * BN + wn * TN + fr] = acc[i][0][r];
+  __syncthreads();
+  float* out = a.out + (long long)g * a.out_gstride;
+  const float* bias = a.bias ? a.bias + (long long)slot * a.b_sstride : nullptr;
+  const float* res = a.res ? a.res + (long long)g * a.out_gstride : nullptr;
+  constexpr int C4 = BN / 4;
+  float vmax = 0.f;
+  for (int e = tid; e < BM * C4; e += 256) {
+    const int row = e / C4, n = (e - row * C4) * 4;
+    const long long o = orow[row];
+    float4 v = *(const float4*)&Ct[row * BN + n];
+    if (bias) { v.x += bias[n]; v.y += bias[n + 1]; v.z += bias[n + 2]; v.w += bias[n + 3]; }
+    if (res) {
+      const float4 rv = *(const float4*)(res + o + n);
+      v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+    }
+    if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    *(float4*)(out + o + n) = v;
+  }
+  if (a.amax_out) amax_fold(a.amax_out, a.amax_out_ld, g, vmax);
+}
+
+// which kernels take their staged-weight form under dba_xstage_set(1) (each where its kernel-bench
+// row beat the parent's by more than three times the parent's run-to-run spread:
+// profiles/r8/xstage/README.md)
+constexpr bool kXStage16Default = true;
+
+// the staged form takes exactly xhalo_try's W-16 evaluation case with whole fragment planes:
+// 3x3 stride-1 pad-1 forward, 16 x 16 x 64 -> 64, pre-split weights, no shortcut / BN / lazy operand
+int xstage16_try(const XArgs& a, int G, int KH, int KW, hipStream_t st) {
+  const XClass& c = a.cls[0];
+  const int mode = xg::xstage_mode();
+  if (!(mode == 3 || (mode == 1 && kXStage16Default))) return -100;
+  if (KH != 3 || KW != 3 || a.sp != 1 || a.os != 1 || a.dsg != 1 || a.splitk != 1 || c.nI != 3 || c.nJ != 3 ||
+      c.bh != -1 || c.bw != -1)
+    return -100;
+  if (a.Hs != 16 || a.Ws != 16 || a.Ho != 16 || a.Wo != 16 || a.Cs != 64 || a.Ncol != 64) return -100;
+  if (a.bf.mode || a.lz_coef || a.sc_src) return -100;
+  if (!aligned16(a.src) || !aligned16(a.w) || a.src_gstride % 4 || a.w_sstride % 4) return -100;
+  if (!a.wp || !a.wf || ((uintptr_t)a.wf & 15) || a.wf_sstride % 8 || a.wf_sstride < 2 * 64 * 576) return -100;
+  hipLaunchKernelGGL(xstage16_kernel, dim3((unsigned)(a.N * (a.Ho / 8)), G, 1), dim3(256), 0, st, a);
+  DBA_LAUNCH_CHECK();
+}
+
 int& ximg_on() {
   static int on = 1;
   return on;
@@ -494,6 +694,18 @@ DBA_EXPORT int dba_xsplit_policy(int target, int min_k, int max_s, int kslab_max
 DBA_EXPORT int dba_ximg_set(int on) {
   const int prev = ximg_on();
   if (on >= 0) ximg_on() = on;
+  return prev;
+}
+
+// the weight path of the fused evaluation block (xblock.hip) and the 16-wide evaluation conv
+// (xstage16_kernel): 1 (default) tap-deep weight stages filled by LDS-DMA from the
+// fragment-ordered planes, in each kernel whose default is on and where the weights carry whole
+// planes (the ring otherwise); 2 the LDS weight ring (same bits: the bit-equality test's and the
+// kernel bench's A/B); 3 the staged form wherever it applies, whatever the kernel's default;
+// negative queries.  Returns the previous setting.
+DBA_EXPORT int dba_xstage_set(int on) {
+  const int prev = xg::xstage_mode();
+  if (on >= 1 && on <= 3) xg::xstage_mode() = on;
   return prev;
 }
 
@@ -553,6 +765,7 @@ DBA_EXPORT int dba_xconv_fwd(const float* x, long long x_gstride, const float* w
   auto fin = [&](int rc) { return (rc == 0 && a.bf.mode) ? bnx_finalize_go(a.bf, nvalid, G, N, Ho * Wo, st) : rc; };
   if (stride == 1) {
     int rc = ximg_try(a, G, KH, KW, st);
+    if (rc == -100) rc = xstage16_try(a, G, KH, KW, st);
     if (rc == -100) rc = xhalo_try(a, G, KH, KW, st);
     if (rc != -100) return fin(rc);
   }

@@ -7,6 +7,13 @@
 #include <type_traits>
 #include <utility>
 
+// the weight path of the evaluation convs with an LDS-DMA staged form (xblock.hip's fused block,
+// xconv_fwd.hip's 16-wide conv), dba_xstage_set: 1 the staged form where the kernel's default is
+// on, 2 the LDS weight ring everywhere, 3 the staged form wherever it applies (xconv_fwd.hip)
+namespace xg {
+int& xstage_mode();
+}
+
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) float f32x2v;

@@ -92,10 +92,11 @@ _SIGS = {
     "dba_bnx_dy": [_P, _P, _P, _P, _LL, _P, _I, _I, _I, _I, _P, _I, _P],
     "dba_xwgrad_reduce_batch": [_P, _I, _I, _LL, _P],
     # fused evaluation BasicBlock, with or without the image stem (csrc/kernels/xblock.hip)
-    "dba_xblock_fwd": [_P, _LL, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 6
+    "dba_xstage_set": [_I],
+    "dba_xblock_fwd": [_P, _LL, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 6
     + [_P, _I, _P, _P, _I, _P, _I, _P],
-    "dba_xblock_stem_fwd": [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 6
-    + [_P, _P, _P, _I, _P, _I, _P],
+    "dba_xblock_stem_fwd": [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P]
+    + [_I] * 6 + [_P, _P, _P, _I, _P, _I, _P],
     "dba_mlp_train": [_P, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I,
                       _P, _LL, _I, _P, _F, _F, _P, _P],
     "dba_xdown_fwd": [_P, _LL, _P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _P] + [_I] * 8
@@ -267,6 +268,15 @@ def set_ximg(on: int) -> int:
     (ximg_kernel: same bits, the A/B), 0 off (the implicit GEMM); -1 queries.  Returns the
     previous setting."""
     return int(_L.dba_ximg_set(int(on)))
+
+
+def set_xstage(on: int) -> int:
+    """Weight path of the fused evaluation BasicBlock (xblock.hip) and the 16-wide evaluation
+    conv (xconv_fwd.hip xstage16_kernel): 1 (default) tap-deep weight stages filled by LDS-DMA from
+    the fragment-ordered planes, in each kernel whose measured default is on and where the weights
+    carry whole planes; 2 the LDS weight ring (same bits, the A/B); 3 the staged form wherever it
+    applies, whatever the kernel's default; -1 queries.  Returns the previous setting."""
+    return int(_L.dba_xstage_set(int(on)))
 
 
 def set_wgrad_halo(on: int) -> int:
@@ -477,6 +487,13 @@ def _wfplanes(w):
     return (None, 0) if p is None else (p.data_ptr(), p.stride(0))
 
 
+def _wfplanes2(w1, w2):
+    """(pointer, pointer, slot stride) of the fragment-ordered planes of a block's two convs, when
+    both carry them with one stride; (None, None, 0) otherwise (the kernel takes its ring form)."""
+    (f1, s1), (f2, s2) = _wfplanes(w1), _wfplanes(w2)
+    return (f1, f2, s1) if f1 is not None and f2 is not None and s1 == s2 else (None, None, 0)
+
+
 def _amax_w(w, gstride, n):
     a = getattr(w, "_dba_amax", None)
     if a is None:
@@ -604,8 +621,8 @@ def basic_block_eval(x, w1, b1, w2, b2, wsel=None, nvalid=None):
     y = torch.empty_like(x)
     ay = _amax_out(y)
     rc = _call("dba_xblock_fwd", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ptr(_i32(wsel)),
-               p1.data_ptr(), p2.data_ptr(), p1.stride(0), b1c.data_ptr(), b2c.data_ptr(), bs1, _ptr(_i32(nvalid)),
-               G, N, W, W, C, C, *_aptr(ax), aw1.data_ptr(), aw2.data_ptr(), aw1.shape[1], *_aptr(ay), _stream())
+               p1.data_ptr(), p2.data_ptr(), p1.stride(0), *_wfplanes2(w1, w2), b1c.data_ptr(), b2c.data_ptr(), bs1,
+               _ptr(_i32(nvalid)), G, N, W, W, C, C, *_aptr(ax), aw1.data_ptr(), aw2.data_ptr(), aw1.shape[1], *_aptr(ay), _stream())
     if rc == NOT_HANDLED:
         raise RuntimeError("xblock_fwd declined a shape basic_block_ok accepted")
     return y
@@ -644,7 +661,7 @@ def stem_block_eval(x, w0, b0, w1, b1, w2, b2, wsel=None, nvalid=None):
     ay = _amax_out(y)
     rc = _call("dba_xblock_stem_fwd", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ptr(_i32(wsel)),
                p0.data_ptr(), p0.stride(0), b0c.data_ptr(), bs0, p1.data_ptr(), p2.data_ptr(), p1.stride(0),
-               b1c.data_ptr(), b2c.data_ptr(), bs1, _ptr(_i32(nvalid)), G, N, W, W, Ci, C, aw0.data_ptr(),
+               *_wfplanes2(w1, w2), b1c.data_ptr(), b2c.data_ptr(), bs1, _ptr(_i32(nvalid)), G, N, W, W, Ci, C, aw0.data_ptr(),
                aw1.data_ptr(), aw2.data_ptr(), aw1.shape[1], *_aptr(ay), _stream())
     if rc == NOT_HANDLED:
         raise RuntimeError("xblock_stem_fwd declined a shape stem_block_ok accepted")

@@ -260,9 +260,11 @@ def main(argv=None) -> int:
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default="", help="substring filter on shape names")
     ap.add_argument("--ximg", type=int, default=-1, help="hip.set_ximg: 1 ximg2_kernel, 2 ximg_kernel, 0 implicit GEMM")
+    ap.add_argument("--xstage", type=int, default=-1, help="hip.set_xstage: 1 LDS-DMA weight stages (each kernel's default), 2 the weight ring, 3 staged everywhere")
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
     H.set_ximg(args.ximg)
+    H.set_xstage(args.xstage)
     rows = []
     for name, G, N, Hh, Cin, Cout, k, s, p in SHAPES:
         if args.only not in name:
