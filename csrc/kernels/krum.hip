@@ -1,0 +1,316 @@
+// Multi-Krum's hot path: D[i][j] = sum_k (x_i[k] - x_j[k])^2 in fp64 over n strided fp32 rows of
+// length L (the clients' final states, read where they lie: rows are picked by an optional index
+// list, and there is no [n, L] fp64 or delta temporary).  The global model cancels out of the
+// difference, so there is no base operand.
+//   * blockIdx.x walks the row length, blockIdx.y the tile pairs (ti <= tj) of the rows.  A block
+//     keeps its tile pair's fp64 accumulators in registers, at most 64 of them (128 VGPRs), and
+//     loads each of its rows once per quad:
+//       - up to kLone = 11 rows are ONE triangular tile (55 pairs): every row is fetched once,
+//         so the n = 10 round case moves n L 4 bytes
+//       - more rows are cut into tiles of kTile = 8: a diagonal tile pair holds its tile's
+//         28 pairs, an off-diagonal one 8 x 8; each row is fetched once per tile pair it is in
+//   * every unordered pair is accumulated once, in exactly one tile pair; the finalize launch sums
+//     its per-block partials in one fixed order (no atomics: bitwise run to run) and writes
+//     D[i][j] and D[j][i] from the same value; the diagonal is written as 0
+//   * which elements a thread takes and the order it adds them in depend only on L and the
+//     launch grid (quad q of every row goes to thread q mod the grid, in ascending q), not on the
+//     rows' alignment, on the tile a pair falls into or on the other rows of the call: the same
+//     bits from an aligned copy and a misaligned view, and from any subset of the rows
+// Rows are read four floats per lane as in clip.hip: one 16-byte load where the row start is
+// 16-byte aligned, four scalar loads otherwise.
+#include "common.hpp"
+#include <algorithm>
+#include <math.h>
+
+// the accumulation below is written with explicit fma(): nothing else is to be contracted
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kQuad = 4;            // floats per lane per step
+constexpr int kTile = 8;            // rows per tile: kTile x kTile fp64 accumulators per thread
+constexpr int kLone = 11;           // most rows of a lone triangular tile: 11 * 10 / 2 = 55 accumulators
+constexpr int kAcc = kTile * kTile;
+constexpr int kMaxRows = 64;
+constexpr int kBlocksMax = 512;     // x 256 threads x 4 floats = 524288 elements per sweep of the grid
+
+static_assert(kLone * (kLone - 1) / 2 <= kAcc && kLone >= kTile, "a triangular tile's pairs fit the accumulators");
+
+__device__ __forceinline__ bool aligned16_dev(const float* p) { return ((uintptr_t)p & 15) == 0; }
+
+// a quad of a row: FULL, four floats at p in one 16-byte load if ``vec`` (a quad's offset from its
+// row start is a multiple of 16 bytes, so ``vec`` is the row start's alignment) or four scalar
+// loads otherwise; else the row's last floats p[0 .. cnt), cnt < 4, zero-filled
+template <bool FULL>
+__device__ __forceinline__ void ld_quad(const float* __restrict__ p, bool vec, int cnt, float (&v)[kQuad]) {
+  if constexpr (FULL) {
+    if (vec) {
+      const float4 x = *(const float4*)p;
+      v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else {
+      v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kQuad; ++j) v[j] = j < cnt ? p[j] : 0.f;
+  }
+}
+
+// the accumulator of local rows (a, b): a triangular (DIAG) tile holds its pairs a < b column by
+// column, an off-diagonal tile pair all kTile x kTile
+template <bool DIAG>
+__device__ __forceinline__ constexpr int acc_slot(int a, int b) {
+  return DIAG ? b * (b - 1) / 2 + a : a * kTile + b;
+}
+
+// the rows of one side of a tile pair: row starts and their alignment
+template <int R>
+struct Rows {
+  const float* p[R];
+  bool vec[R];
+  int n;                            // rows in use (the others repeat the last one and are never read)
+};
+
+template <int R>
+__device__ __forceinline__ void rows_init(Rows<R>& t, const float* __restrict__ buf, long long rstride,
+                                          const int* __restrict__ row_idx, int r0, int cnt) {
+  t.n = cnt;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int row = r0 + min(r, cnt - 1);
+    t.p[r] = buf + (long long)(row_idx ? row_idx[row] : row) * rstride;
+    t.vec[r] = aligned16_dev(t.p[r]);
+  }
+}
+
+// one quad (floats k .. k + cnt of every row of the tile pair) into the accumulators.  (x_a - x_b)
+// is exact in fp64; one rounding per fma; the zero fill of a row's last quad adds 0.  The loads
+// of the A rows (all the rows of a DIAG tile) are issued before the first use; the B rows of an
+// off-diagonal pair come kBPart at a time, which keeps the step within 256 registers.
+constexpr int kBPart = 4;
+
+template <bool DIAG, int RA, int NB>
+__device__ __forceinline__ void pair_acc(const float (&xa)[RA][kQuad], const float (&xb)[NB][kQuad], int na, int nb,
+                                         int b0, double (&acc)[kAcc]) {
+#pragma unroll
+  for (int bb = 0; bb < NB; ++bb) {
+    const int b = b0 + bb;          // (a compile-time constant once unrolled: b0 is one at every call)
+    if (b < nb) {
+      double yb[kQuad];
+#pragma unroll
+      for (int j = 0; j < kQuad; ++j) yb[j] = (double)xb[bb][j];
+#pragma unroll
+      for (int a = 0; a < RA; ++a) {
+        if (DIAG ? a < b : a < na) {
+#pragma unroll
+          for (int j = 0; j < kQuad; ++j) {
+            const double d = (double)xa[a][j] - yb[j];
+            acc[acc_slot<DIAG>(a, b)] = fma(d, d, acc[acc_slot<DIAG>(a, b)]);
+          }
+        }
+      }
+    }
+  }
+}
+
+// the quad at float k of every row in use
+template <bool FULL, int R>
+__device__ __forceinline__ void load_rows(const Rows<R>& t, long long k, int cnt, float (&x)[R][kQuad]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r < t.n) ld_quad<FULL>(t.p[r] + k, t.vec[r], cnt, x[r]);
+}
+
+template <bool DIAG, bool FULL, int RA, int RB>
+__device__ __forceinline__ void pair_step(const Rows<RA>& ta, const Rows<RB>& tb, long long k, int cnt,
+                                          double (&acc)[kAcc]) {
+  float xa[RA][kQuad];
+  load_rows<FULL>(ta, k, cnt, xa);
+  if constexpr (DIAG) {
+    pair_acc<true>(xa, xa, ta.n, ta.n, 0, acc);
+  } else {
+#pragma unroll
+    for (int h = 0; h < RB; h += kBPart) {
+      float xb[kBPart][kQuad];
+#pragma unroll
+      for (int r = 0; r < kBPart; ++r)
+        if (h + r < tb.n) ld_quad<FULL>(tb.p[h + r] + k, tb.vec[h + r], cnt, xb[r]);
+      pair_acc<false>(xa, xb, ta.n, tb.n, h, acc);
+    }
+  }
+}
+
+// pair (i < j) -> its slot in the partials: row-major order of the strict upper triangle
+__device__ __forceinline__ long long pair_slot(int i, int j, int n) {
+  return (long long)i * (2 * n - i - 1) / 2 + (j - i - 1);
+}
+
+// a block's share of one tile pair: rows a0 .. a0 + na against rows b0 .. b0 + nb (DIAG: the same
+// tile, pairs a < b), partials to part[pair_slot][blockIdx.x]
+template <bool DIAG, int RA, int RB>
+__device__ __forceinline__ void tile_pair_body(const float* __restrict__ buf, long long rstride,
+                                               const int* __restrict__ row_idx, int n, long long L, int a0, int na,
+                                               int b0, int nb, double* __restrict__ part, double (&red)[4][kAcc]) {
+  Rows<RA> ta;
+  Rows<RB> tb;
+  rows_init(ta, buf, rstride, row_idx, a0, na);
+  rows_init(tb, buf, rstride, row_idx, b0, nb);
+  double acc[kAcc];
+#pragma unroll
+  for (int s = 0; s < kAcc; ++s) acc[s] = 0.0;
+
+  // whole quads in ascending order, then the row's last, partial quad (one thread of the launch)
+  const long long nq = (L + kQuad - 1) / kQuad, nfull = L / kQuad;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if constexpr (DIAG) {
+    // a triangular tile has the registers to issue the next quad's loads before this quad's
+    // arithmetic (the same quads in the same order)
+    if (q < nfull) {
+      float xa[RA][kQuad];
+      load_rows<true>(ta, q * kQuad, kQuad, xa);
+      for (;;) {
+        const long long qn = q + stride;
+        if (qn >= nfull) break;
+        float xn[RA][kQuad];
+        load_rows<true>(ta, qn * kQuad, kQuad, xn);
+        pair_acc<true>(xa, xa, na, na, 0, acc);
+#pragma unroll
+        for (int r = 0; r < RA; ++r)
+#pragma unroll
+          for (int j = 0; j < kQuad; ++j) xa[r][j] = xn[r][j];      // (rows not in use: never read)
+        q = qn;
+      }
+      pair_acc<true>(xa, xa, na, na, 0, acc);
+      q += stride;
+    }
+  } else {
+    for (; q < nfull; q += stride) pair_step<DIAG, true>(ta, tb, q * kQuad, kQuad, acc);
+  }
+  if (q < nq) pair_step<DIAG, false>(ta, tb, q * kQuad, (int)(L - q * kQuad), acc);
+
+  // lanes in a fixed butterfly, then the four waves in order
+#pragma unroll
+  for (int b = DIAG ? 1 : 0; b < (DIAG ? RA : RB); ++b) {
+#pragma unroll
+    for (int a = 0; a < RA; ++a) {
+      if (b < nb && (DIAG ? a < b : a < na)) {
+        double s = acc[acc_slot<DIAG>(a, b)];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][acc_slot<DIAG>(a, b)] = s;
+      }
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < kAcc) {
+    int a, b;
+    if (DIAG) {                    // t = b (b - 1) / 2 + a, a < b
+      b = 1;
+      a = t;
+      while (a >= b) {
+        a -= b;
+        ++b;
+      }
+    } else {
+      a = t / kTile;
+      b = t % kTile;
+    }
+    if (a < na && b < nb)
+      part[pair_slot(a0 + a, b0 + b, n) * gridDim.x + blockIdx.x] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+  }
+}
+
+// n <= kLone rows as one triangular tile (a kernel of its own: its registers are not the tiled one's)
+__global__ __launch_bounds__(256) void pairwise_sqdist_lone_kernel(const float* __restrict__ buf, long long rstride,
+                                                                   const int* __restrict__ row_idx, int n, long long L,
+                                                                   double* __restrict__ part) {
+  __shared__ double red[4][kAcc];
+  tile_pair_body<true, kLone, kLone>(buf, rstride, row_idx, n, L, 0, n, 0, n, part, red);
+}
+
+// n > kLone rows in tiles of kTile
+__global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __restrict__ buf, long long rstride,
+                                                              const int* __restrict__ row_idx, int n, long long L,
+                                                              double* __restrict__ part) {
+  __shared__ double red[4][kAcc];
+  // tile pair blockIdx.y in row-major order of the upper triangle of nt x nt tiles
+  const int nt = (n + kTile - 1) / kTile;
+  int ti = 0, tj = blockIdx.y;
+  while (tj >= nt - ti) {
+    tj -= nt - ti;
+    ++ti;
+  }
+  tj += ti;
+  const int a0 = ti * kTile, b0 = tj * kTile;
+  const int na = min(kTile, n - a0), nb = min(kTile, n - b0);
+  if (ti == tj) {
+    if (na >= 2)                   // (a last tile of one row holds no pair of its own)
+      tile_pair_body<true, kTile, kTile>(buf, rstride, row_idx, n, L, a0, na, a0, na, part, red);
+  } else {
+    tile_pair_body<false, kTile, kTile>(buf, rstride, row_idx, n, L, a0, na, b0, nb, part, red);
+  }
+}
+
+// one wave per pair: lane l takes the partials of blocks l, l + 64, ... in that order, then the
+// lanes combine in a fixed butterfly (delta_stats_finalize's order); the n blocks after the pairs
+// write the diagonal
+__global__ __launch_bounds__(64) void pairwise_sqdist_finalize(const double* __restrict__ part, int nblk, int n,
+                                                              double* __restrict__ out) {
+  const int npairs = n * (n - 1) / 2;
+  int t = blockIdx.x;
+  if (t >= npairs) {
+    if (threadIdx.x == 0) out[(long long)(t - npairs) * (n + 1)] = 0.0;
+    return;
+  }
+  const long long slot = t;
+  int i = 0;
+  while (t >= n - 1 - i) {
+    t -= n - 1 - i;
+    ++i;
+  }
+  const int j = i + 1 + t;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += kWave) s += part[slot * nblk + b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+  if (threadIdx.x == 0) {
+    out[(long long)i * n + j] = s;
+    out[(long long)j * n + i] = s;
+  }
+}
+
+}  // namespace
+
+// per-pair partials of a call over rows of length L: the workspace is n (n - 1) / 2 times as many doubles
+DBA_EXPORT int dba_pairwise_sqdist_blocks(long long L) {
+  const long long nq = (L + kQuad - 1) / kQuad;
+  return (int)std::max(1LL, std::min((long long)kBlocksMax, (nq + 255) / 256));
+}
+
+// out [n][n] fp64 = squared L2 distances between rows row_idx[r] (r if row_idx is null) of buf, each
+// of L floats, rstride floats apart; 2 <= n <= 64 (hipErrorInvalidValue beyond: the caller composes
+// larger sets).  part: [n (n - 1) / 2][dba_pairwise_sqdist_blocks(L)] fp64 workspace (no
+// initialisation needed).  n < 2 or L = 0: zeros, without a launch of the pass over the rows.
+DBA_EXPORT int dba_pairwise_sqdist(const float* buf, long long rstride, const int* row_idx, int n, long long L,
+                                   double* out, double* part, void* stream) {
+  if (n <= 0) return 0;
+  if (n > kMaxRows) return (int)hipErrorInvalidValue;
+  if (n < 2 || L <= 0) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(double) * n * n, (hipStream_t)stream);
+    return (int)e;
+  }
+  const int bx = dba_pairwise_sqdist_blocks(L);
+  if (n <= kLone) {
+    hipLaunchKernelGGL(pairwise_sqdist_lone_kernel, dim3(bx), dim3(256), 0, (hipStream_t)stream, buf, rstride, row_idx,
+                       n, L, part);
+  } else {
+    const int nt = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(pairwise_sqdist_kernel, dim3(bx, nt * (nt + 1) / 2), dim3(256), 0, (hipStream_t)stream, buf,
+                       rstride, row_idx, n, L, part);
+  }
+  hipLaunchKernelGGL(pairwise_sqdist_finalize, dim3(n * (n - 1) / 2 + n), dim3(kWave), 0, (hipStream_t)stream, part, bx,
+                     n, out);
+  DBA_LAUNCH_CHECK();
+}

@@ -128,6 +128,13 @@ _DEFAULTS: Dict[str, Any] = {
     # median of the round's client update norms.  With diff_privacy the noise then sits on a sum
     # of bounded sensitivity
     "clip_norm": None,
+    # Multi-Krum (aggregation "mean" only; Blanchard et al., NeurIPS 2017): each client is scored
+    # by the sum of its n - f - 2 smallest squared distances to the other clients' final states and
+    # the m best-scored clients are averaged.  krum_f: None = off; an integer >= 0 = f, the number
+    # of Byzantine clients tolerated per round (needs n >= 2 f + 3).  krum_m: None = n - f
+    # (Multi-Krum); an integer in 1 .. n - f = m (1 is the original Krum)
+    "krum_f": None,
+    "krum_m": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -163,6 +170,17 @@ class Params(dict):
         if self.clip_norm is not None and self["aggregation_methods"] != AGGR_MEAN:
             raise ValueError(f"clip_norm is an option of aggregation {AGGR_MEAN!r} "
                              f"(got {self['aggregation_methods']!r})")
+        f, m = self.krum_f, self.krum_m
+        if f is None:
+            if m is not None:
+                raise ValueError("krum_m is set without krum_f")
+        else:
+            if self["aggregation_methods"] != AGGR_MEAN:
+                raise ValueError(f"krum_f is an option of aggregation {AGGR_MEAN!r} "
+                                 f"(got {self['aggregation_methods']!r})")
+            if self.clip_norm is not None:
+                raise ValueError("krum_f and clip_norm cannot be combined")
+            check_krum_sizes(int(self["no_models"]), f, m, "no_models")
 
     @property
     def type(self) -> str:
@@ -172,6 +190,16 @@ class Params(dict):
     def clip_norm(self) -> Any:
         """The checked ``clip_norm``: None (off), the bound C as a float, or ``"median"``."""
         return check_clip_norm(self.get("clip_norm"))
+
+    @property
+    def krum_f(self) -> Optional[int]:
+        """The checked ``krum_f``: None (Multi-Krum off) or f >= 0."""
+        return check_krum_int("krum_f", self.get("krum_f"), 0)
+
+    @property
+    def krum_m(self) -> Optional[int]:
+        """The checked ``krum_m``: None (m = n - f) or m >= 1."""
+        return check_krum_int("krum_m", self.get("krum_m"), 1)
 
     @property
     def adversary_list(self) -> List[Any]:
@@ -231,6 +259,27 @@ def check_clip_norm(v: Any) -> Any:
     if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
         return float(v)
     raise ValueError(f"clip_norm {v!r}: expected None, a finite number > 0 or {CLIP_MEDIAN!r}")
+
+
+def check_krum_int(key: str, v: Any, lo: int) -> Optional[int]:
+    """None or an integer >= ``lo`` (a bool, a float or a string is an error)."""
+    if v is None:
+        return None
+    if isinstance(v, int) and not isinstance(v, bool) and v >= lo:
+        return v
+    raise ValueError(f"{key} {v!r}: expected None or an integer >= {lo}")
+
+
+def check_krum_sizes(n: int, f: int, m: Optional[int], what: str = "n") -> int:
+    """Multi-Krum's two inequalities for n clients: n >= 2 f + 3 (so every score sums n - f - 2 >=
+    f + 1 >= 1 distances) and m <= n - f.  Returns m (``n - f`` when None)."""
+    if n < 2 * f + 3:
+        raise ValueError(f"krum_f {f} needs {what} >= 2 f + 3 = {2 * f + 3} (got {n})")
+    if m is None:
+        return n - f
+    if m > n - f:
+        raise ValueError(f"krum_m {m} exceeds {what} - krum_f = {n - f}")
+    return m
 
 
 def _same_client(a: Any, b: Any) -> bool:

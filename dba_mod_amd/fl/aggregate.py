@@ -16,6 +16,11 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   fused HIP passes over the strided client rows (``ops.delta_stats``,
   ``ops.clipped_delta_sum_fixed``); the products ``s_i delta_i`` are not exactly summable in
   fp64, so the sum goes through the same fixed-point limbs as RFA / FoolsGold.
+* :func:`fedavg_krum` / :func:`krum_scores` / :func:`krum_select` — Multi-Krum (config ``krum_f``,
+  ``krum_m``; Blanchard et al., NeurIPS 2017; not in the reference): the clients farthest from the
+  crowd are dropped and the rest averaged.  The [n, n] squared distances between the final states
+  come from one fused HIP pass (``ops.pairwise_sq_dists``: fp64 differences, no atomics, a pair's
+  bits independent of the other rows); scores and selection are host fp64 arithmetic.
 * :func:`geometric_median` / :func:`geometric_median_distributed` — RFA / Weiszfeld,
   ``helper.py:295-373`` (the latter with the points resident on their owner ranks): one batched distance
   kernel (all n clients in one pass) and one weighted-sum kernel per iteration; weights and
@@ -156,6 +161,63 @@ def fedavg_clipped(global_state: torch.Tensor, finals: torch.Tensor, clip, eta: 
     total = part if E is None else fixed_decode(part, E)
     ops.add_noise_scaled(global_state[:n_update], total, eta / no_models, sigma, seed, dp)
     return [float(x) for x in factors], [float(x) for x in sq.double().cpu().sqrt()]
+
+
+def krum_scores(D: torch.Tensor, f: int) -> torch.Tensor:
+    """Krum scores (fp64 [n], on the host) from the [n, n] squared-distance matrix: score_i is
+    the sum, in ascending order, of the n - f - 2 smallest D[i][j], j != i.  Non-finite entries
+    of D (a NaN / Inf client state) count as +inf, so such a client scores +inf and pushes nobody
+    else's score up unless fewer than n - f - 2 finite neighbours remain.  Host fp64 arithmetic on
+    a matrix every rank holds with the same bits: every rank computes the same scores."""
+    D = D.detach().double().cpu()
+    n = D.shape[0]
+    k = n - f - 2
+    if k < 1:
+        raise ValueError(f"krum: n = {n} clients need n >= f + 3 (f = {f}) to score")
+    inf = torch.full_like(D, math.inf)
+    D = torch.where(torch.isfinite(D), D, inf)
+    scores = torch.empty(n, dtype=torch.float64)
+    for i in range(n):
+        row = torch.sort(torch.cat([D[i, :i], D[i, i + 1:]])).values[:k]
+        s = 0.0
+        for v in row.tolist():
+            s += v
+        scores[i] = s
+    return scores
+
+
+def krum_select(scores: torch.Tensor, m: int) -> List[int]:
+    """The (sorted) indices of the ``m`` smallest scores, ties to the lower index; a client with
+    an infinite score is never selected, so fewer than ``m`` come back when fewer are finite, and
+    none finite is an error."""
+    s = scores.detach().double().cpu()
+    order = torch.sort(s, stable=True).indices.tolist()
+    sel = [i for i in order if math.isfinite(float(s[i]))][:m]
+    if not sel:
+        raise RuntimeError("krum: no client has a finite score (every client state is non-finite)")
+    return sorted(sel)
+
+
+def fedavg_krum(global_state: torch.Tensor, finals: torch.Tensor, f: int, m: Optional[int], eta: float,
+                dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
+    """In-place Multi-Krum of ``finals`` [n, S] (single rank): the squared distances between the
+    clients' states over the ``n_update`` leading entries (exactly the entries aggregated;
+    ``ops.pairwise_sq_dists``: one fused HIP pass), the scores, the ``m`` (default n - f) best, then
+    ``w += (eta / m_sel) * sum_{i selected} (finals_i - w) (+ noise)`` with the plain FedAvg delta
+    sum over the selected rows in client order.  Returns (selected mask [n], scores [n])."""
+    n = finals.shape[0]
+    D = ops.pairwise_sq_dists(finals[:, :n_update])
+    scores = krum_scores(D, f)
+    sel = krum_select(scores, n - f if m is None else m)
+    krum_apply(global_state, finals[sel], len(sel), eta, dp, sigma, seed, n_update)
+    return [1.0 if i in sel else 0.0 for i in range(n)], [float(x) for x in scores]
+
+
+def krum_apply(global_state: torch.Tensor, selected: torch.Tensor, m_sel: int, eta: float, dp: bool, sigma: float,
+               seed: int, n_update: int) -> None:
+    """``w += (eta / m_sel) * sum_i (selected_i - w) (+ noise)`` over the gathered selected rows."""
+    total = ops.delta_sum(selected[:, :n_update], global_state[:n_update])
+    ops.add_noise_scaled(global_state[:n_update], total, eta / m_sel, sigma, seed, dp)
 
 
 def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol: float, poll: int = 0):

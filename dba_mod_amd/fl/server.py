@@ -215,9 +215,10 @@ class Server:
         if rounds <= 0:
             return
         p = self.params
-        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm")}
+        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm", "krum_f", "krum_m")}
         # (plain FedAvg: the warm start stands in for a checkpoint trained without a defence)
-        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None})
+        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None,
+                  "krum_f": None, "krum_m": None})
         if lr is not None:
             p["lr"] = float(lr)
         try:
@@ -534,7 +535,8 @@ class Server:
         Client snapshots stay on their owner rank.  Only the rows some other rank reads are
         broadcast from their owners: the snapshots of clients whose tests are image-sharded across ranks
         (the round's longest clients, or every client without early local tests) and, for
-        RFA in gather mode, the final states.  Aggregation itself reduces (``_aggregate``)."""
+        RFA in gather mode and for Multi-Krum, the final states.  Aggregation itself reduces
+        (``_aggregate``)."""
         S, P = self.spec.S, self.spec.P
         world, rank = self.d.world, self.d.rank
         by_name = {r.name: r for r in results}
@@ -557,7 +559,9 @@ class Server:
                 done_early = early.done if early is not None else set()
                 shared.update(plan.jobs[j].model for j in range(len(plan.jobs))
                               if j not in done_early and plan.jobs[j].model != 0)
-            if (self.params["aggregation_methods"] == C.AGGR_GEO_MED and self._rfa_gather(len(plan.clients))):
+            if ((self.params["aggregation_methods"] == C.AGGR_GEO_MED and self._rfa_gather(len(plan.clients)))
+                    or self.params.krum_f is not None):
+                # (Multi-Krum scores every client against every other: every rank needs every final row)
                 shared.update(c.final_snap for c in plan.clients)
             for s, t in local_snaps.items():
                 bank[s] = t
@@ -627,6 +631,8 @@ class Server:
         dp_seed = (int(p["seed"]) * 7919 + plan.epoch) & 0x7FFFFFFF
         if method == C.AGGR_MEAN and p.clip_norm is not None:
             self._aggregate_clipped(plan, local, names, adversarial, p.clip_norm, n_upd, dp_seed)
+        elif method == C.AGGR_MEAN and p.krum_f is not None:
+            self._aggregate_krum(plan, bank, names, adversarial, p.krum_f, p.krum_m, n_upd, dp_seed)
         elif method == C.AGGR_MEAN:
             # each rank sums its own clients' deltas (fp64), one all-reduce of S values
             part = ops.delta_sum(local["finals"][:, :n_upd], self.global_state[:n_upd])
@@ -715,6 +721,31 @@ class Server:
         log.info(f"[clip agg] C: {bound}  clipped: {int((norms > bound).sum())}/{n}  factors: {fl}")
         self.csv.add_weight_result(names, fl, nl)
         self._plot_weights(names, fl, nl, adversarial, plan.epoch)
+
+    def _aggregate_krum(self, plan: RoundPlan, bank: torch.Tensor, names: List[Any], adversarial: List[Any],
+                        f: int, m: Optional[int], n_upd: int, dp_seed: int) -> None:
+        """Multi-Krum (``krum_f``) on the gathered final states: ``_gather`` has broadcast every
+        client's final row into every rank's bank, so every rank computes the [n, n] squared
+        distances from the bank rows in place (one fused pass, the rows picked by their slots),
+        scores, selects and applies the selected clients' FedAvg redundantly.  No collective
+        follows the gather: the same rows in the same order through the same kernel give every
+        rank, at every world size, the same bits."""
+        p = self.params
+        n = len(plan.clients)
+        m = C.check_krum_sizes(n, f, m, "the round's clients")
+        slots = [c.final_snap for c in plan.clients]
+        D = ops.pairwise_sq_dists(bank[:, :n_upd], slots)
+        scores = agg.krum_scores(D, f)
+        sel = agg.krum_select(scores, m)
+        agg.krum_apply(self.global_state, bank[[slots[i] for i in sel]], len(sel), float(p["eta"]),
+                       bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
+        mask = [1.0 if i in sel else 0.0 for i in range(n)]
+        sc = [float(x) for x in scores]
+        chosen = [names[i] for i in sel]
+        log.info(f"[krum agg] f: {f}  m: {m}  selected: {chosen}  "
+                 f"adversaries selected: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}")
+        self.csv.add_weight_result(names, mask, sc)
+        self._plot_weights(names, mask, sc, adversarial, plan.epoch)
 
     def _log_poison_ratio(self, tag: str, names: List[Any], ns: List[int]) -> None:
         p = self.params

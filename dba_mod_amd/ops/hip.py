@@ -15,6 +15,7 @@ import torch
 
 from . import bnstate as bs
 from . import build
+from . import reference as _ref
 
 Tensor = torch.Tensor
 _F32 = torch.float32
@@ -65,6 +66,9 @@ _SIGS = {
     "dba_delta_stats": [_P, _LL, _I, _P, _LL, _P, _P, _P, _P, _P],
     "dba_clipped_delta_sum_fixed": [_P, _LL, _I, _P, _P, _P, _LL, _D, _P],
     "dba_clipped_delta_sum": [_P, _LL, _I, _P, _P, _P, _LL, _P],
+    # Multi-Krum pairwise distances (csrc/kernels/krum.hip)
+    "dba_pairwise_sqdist_blocks": [_LL],
+    "dba_pairwise_sqdist": [_P, _LL, _P, _I, _LL, _P, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
@@ -1372,6 +1376,38 @@ def clipped_delta_sum(rows, base, scale):
     out = torch.empty(L, dtype=torch.float64, device=base.device)
     _call("dba_clipped_delta_sum", rows.data_ptr(), rs, n, base.data_ptr(), scale.data_ptr(), out.data_ptr(), L,
           _stream())
+    return out
+
+
+PAIRWISE_MAX_ROWS = 64     # krum.hip kMaxRows
+
+
+def pairwise_sq_dists(buf, row_idx=None):
+    """fp64 [n, n] squared L2 distances between rows of ``buf`` [R, L] (krum.hip): the rows are read
+    where they lie (``row_idx``: n row numbers into ``buf``, repeats allowed), every unordered pair
+    accumulated once in fp64 and mirrored; no atomics, bitwise run to run, and a pair's bits do
+    not depend on the rows' alignment or on the other rows of the call.  More than 64 rows take
+    the reference composition on the device."""
+    assert buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
+    if buf.shape[1] > 1 and buf.stride(1) != 1:
+        buf = buf.contiguous()
+    R, L = buf.shape
+    idx = None
+    if row_idx is not None:
+        rows = [int(r) for r in (row_idx.tolist() if isinstance(row_idx, Tensor) else row_idx)]
+        if not all(0 <= r < R for r in rows):       # (the kernel reads rows[r] * stride unchecked)
+            raise ValueError(f"pairwise_sq_dists: row_idx {rows} outside the {R} rows of buf")
+        idx = torch.tensor(rows, dtype=torch.int32, device=buf.device)
+    n = R if idx is None else idx.numel()
+    if n > PAIRWISE_MAX_ROWS:
+        return _ref.pairwise_sq_dists(buf, row_idx)
+    if n < 2 or L == 0:
+        return torch.zeros(n, n, dtype=torch.float64, device=buf.device)
+    rs = buf.stride(0) if R > 1 else L
+    out = torch.empty(n, n, dtype=torch.float64, device=buf.device)
+    nb = int(_L.dba_pairwise_sqdist_blocks(L))
+    part = torch.empty(n * (n - 1) // 2 * nb, dtype=torch.float64, device=buf.device)
+    _call("dba_pairwise_sqdist", buf.data_ptr(), rs, _ptr(idx), n, L, out.data_ptr(), part.data_ptr(), _stream())
     return out
 
 

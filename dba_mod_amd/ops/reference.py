@@ -605,6 +605,35 @@ def clipped_delta_sum(rows: Tensor, base: Tensor, scale: Tensor) -> Tensor:
     return (scale.float().double()[:, None] * (rows.double() - base.double()[None])).sum(0)
 
 
+PAIRWISE_CHUNK = 1 << 18
+
+
+def pairwise_sq_dists(buf: Tensor, row_idx=None) -> Tensor:
+    """fp64 [n, n] squared L2 distances between the rows of ``buf`` [R, L] fp32 (Multi-Krum;
+    krum.hip pairwise_sqdist_kernel is the GPU form): rows ``row_idx`` (n row numbers, repeats
+    allowed) or all of them.  The pair difference is taken in fp64 (exact for fp32 rows: the
+    Gram formula g_ii + g_jj - 2 g_ij would cancel the digits that carry the distance between
+    nearly equal client states).  Chunked over L, so no [n, n, L] temporary; each unordered pair
+    is summed once and mirrored: symmetric, zero diagonal.  A NaN / Inf element makes its row's
+    off-diagonal distances non-finite and leaves the others alone."""
+    assert buf.dim() == 2
+    idx = None
+    if row_idx is not None:
+        idx = torch.as_tensor(row_idx, dtype=torch.int64, device=buf.device).reshape(-1)
+    n = buf.shape[0] if idx is None else idx.numel()
+    L = buf.shape[1]
+    D = torch.zeros(n, n, dtype=torch.float64, device=buf.device)
+    if n < 2:
+        return D
+    for c0 in range(0, L, PAIRWISE_CHUNK):
+        x = buf[:, c0:c0 + PAIRWISE_CHUNK]
+        x = (x if idx is None else x.index_select(0, idx)).double()
+        for i in range(n - 1):
+            d = x[i + 1:] - x[i][None]
+            D[i, i + 1:] += (d * d).sum(1)
+    return D + D.t()
+
+
 def gram(feats: Tensor) -> Tensor:
     """F F^T in float64 (K15)."""
     f = feats.double()

@@ -254,6 +254,47 @@ def _bench_clip(name, n, S, reps, dev):
             "composed_us": round((t_delta + t_sqd + t_wsum) * 1e6, 1)}
 
 
+# Multi-Krum (krum.hip): the [n, n] squared distances between a CIFAR round's 10 final states
+KRUM = [("krum.cifar", 10, 2_802_430)]
+
+
+def _bench_krum(name, n, S, reps, dev):
+    """The fused pairwise-distance kernel, reading the final-state rows where they lie in a
+    snapshot bank, against the composition it replaces: the [n, S] copy of those rows, then n
+    calls of sq_dists(points, points[i]).  GB/s counts n * S * 4 bytes for both: the bytes a
+    perfect kernel would move (the fused kernel fetches each row about twice, the composition
+    n + 2 times)."""
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    bank = base[None] + 0.01 * torch.randn(2 * n + 1, S, device=dev)      # finals in the odd slots
+    slots = torch.arange(1, 2 * n + 1, 2, device=dev)
+    rows = bank[1::2]                                                     # the same rows as a strided view
+    assert rows.shape[0] == n and torch.equal(rows, bank[slots])
+
+    def composed():
+        points = bank[slots]
+        return torch.stack([H.sq_dists(points, points[i]) for i in range(n)])
+
+    D = H.pairwise_sq_dists(rows)
+    Dc = composed()
+    rel = float(((D - Dc).abs() / Dc.clamp_min(1e-300)).max())
+    t_fused = _time(lambda: H.pairwise_sq_dists(rows), reps)
+    # (S is even but no multiple of 4: the bank's odd rows start 8 bytes off a 16-byte boundary
+    # and take the scalar-load path; a padded copy has every row aligned)
+    pad = torch.zeros(n, (S + 3) // 4 * 4, device=dev)
+    pad[:, :S] = rows
+    assert torch.equal(H.pairwise_sq_dists(pad[:, :S]), D)
+    t_aligned = _time(lambda: H.pairwise_sq_dists(pad[:, :S]), reps)
+    t_comp = _time(composed, reps)
+    t_copy = _time(lambda: bank[slots], reps)
+    b = n * S * 4
+    return {"shape": name, "n": n, "S": S, "fused_us": round(t_fused * 1e6, 1),
+            "fused_GBps": round(b / t_fused / 1e9, 1), "fused_aligned_us": round(t_aligned * 1e6, 1),
+            "fused_aligned_GBps": round(b / t_aligned / 1e9, 1), "composed_us": round(t_comp * 1e6, 1),
+            "composed_GBps": round(b / t_comp / 1e9, 1), "composed_copy_us": round(t_copy * 1e6, 1),
+            "fused_vs_composed_max_rel": rel}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -282,6 +323,10 @@ def main(argv=None) -> int:
     for name, n, S in CLIP:
         if args.only in name:
             rows.append(_bench_clip(name, n, S, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, n, S in KRUM:
+        if args.only in name:
+            rows.append(_bench_krum(name, n, S, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
