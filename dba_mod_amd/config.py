@@ -135,6 +135,11 @@ _DEFAULTS: Dict[str, Any] = {
     # (Multi-Krum); an integer in 1 .. n - f = m (1 is the original Krum)
     "krum_f": None,
     "krum_m": None,
+    # coordinate-wise trimmed mean / median (aggregation "mean" only; Yin et al., ICML 2018): per
+    # coordinate the k smallest and k largest of the n client values are dropped and the rest
+    # averaged.  None = off; an integer k >= 1 (needs n >= 2 k + 1); "median" = k = (n - 1) // 2,
+    # the coordinate-wise median (the mean of the two middle values for even n)
+    "trim_k": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -181,6 +186,14 @@ class Params(dict):
             if self.clip_norm is not None:
                 raise ValueError("krum_f and clip_norm cannot be combined")
             check_krum_sizes(int(self["no_models"]), f, m, "no_models")
+        t = self.trim_k
+        if t is not None:
+            if self["aggregation_methods"] != AGGR_MEAN:
+                raise ValueError(f"trim_k is an option of aggregation {AGGR_MEAN!r} "
+                                 f"(got {self['aggregation_methods']!r})")
+            if self.clip_norm is not None or f is not None:
+                raise ValueError("trim_k cannot be combined with clip_norm or krum_f")
+            check_trim_sizes(int(self["no_models"]), t, "no_models")
 
     @property
     def type(self) -> str:
@@ -200,6 +213,11 @@ class Params(dict):
     def krum_m(self) -> Optional[int]:
         """The checked ``krum_m``: None (m = n - f) or m >= 1."""
         return check_krum_int("krum_m", self.get("krum_m"), 1)
+
+    @property
+    def trim_k(self) -> Any:
+        """The checked ``trim_k``: None (off), k >= 1 or ``"median"``."""
+        return check_trim_k(self.get("trim_k"))
 
     @property
     def adversary_list(self) -> List[Any]:
@@ -280,6 +298,27 @@ def check_krum_sizes(n: int, f: int, m: Optional[int], what: str = "n") -> int:
     if m > n - f:
         raise ValueError(f"krum_m {m} exceeds {what} - krum_f = {n - f}")
     return m
+
+
+TRIM_MEDIAN = "median"
+
+
+def check_trim_k(v: Any) -> Any:
+    """None, an integer k >= 1 or ``"median"`` (a bool, a float or another string is an error)."""
+    if v is None or (isinstance(v, str) and v == TRIM_MEDIAN):
+        return v
+    if isinstance(v, int) and not isinstance(v, bool) and v >= 1:
+        return v
+    raise ValueError(f"trim_k {v!r}: expected None, an integer >= 1 or {TRIM_MEDIAN!r}")
+
+
+def check_trim_sizes(n: int, trim_k: Any, what: str = "n") -> int:
+    """The trim count k for n clients: ``trim_k``, or (n - 1) // 2 for ``"median"``; n >= 2 k + 1
+    (so at least one value per coordinate is kept) and n >= 1."""
+    k = (n - 1) // 2 if trim_k == TRIM_MEDIAN else int(trim_k)
+    if n < 1 or n < 2 * k + 1:
+        raise ValueError(f"trim_k {trim_k} needs {what} >= 2 k + 1 = {2 * max(k, 0) + 1} (got {n})")
+    return k
 
 
 def _same_client(a: Any, b: Any) -> bool:

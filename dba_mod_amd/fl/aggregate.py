@@ -21,6 +21,12 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   crowd are dropped and the rest averaged.  The [n, n] squared distances between the final states
   come from one fused HIP pass (``ops.pairwise_sq_dists``: fp64 differences, no atomics, a pair's
   bits independent of the other rows); scores and selection are host fp64 arithmetic.
+* :func:`fedavg_trimmed` / :func:`trim_count` — coordinate-wise trimmed mean / median (config
+  ``trim_k``; Yin et al., ICML 2018; not in the reference): per coordinate the k smallest and k
+  largest client values are dropped and the rest averaged; no per-client decision.  One fused HIP
+  pass over the strided final states (``ops.trimmed_delta_sum``: each coordinate sorted in
+  registers, the kept ranks added in ascending order in fp64, so every bit is fixed by IEEE
+  arithmetic) also counts, per client, the coordinates at which it was kept or cut.
 * :func:`geometric_median` / :func:`geometric_median_distributed` — RFA / Weiszfeld,
   ``helper.py:295-373`` (the latter with the points resident on their owner ranks): one batched distance
   kernel (all n clients in one pass) and one weighted-sum kernel per iteration; weights and
@@ -43,6 +49,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .. import config as C
 from .. import ops
 
 log = logging.getLogger("logger")
@@ -218,6 +225,39 @@ def krum_apply(global_state: torch.Tensor, selected: torch.Tensor, m_sel: int, e
     """``w += (eta / m_sel) * sum_i (selected_i - w) (+ noise)`` over the gathered selected rows."""
     total = ops.delta_sum(selected[:, :n_update], global_state[:n_update])
     ops.add_noise_scaled(global_state[:n_update], total, eta / m_sel, sigma, seed, dp)
+
+
+def trim_count(n: int, trim_k) -> int:
+    """The trim count k of a round of n clients: ``trim_k`` itself, or (n - 1) // 2 for
+    ``"median"`` (the coordinate-wise median: the middle value for odd n, the mean of the two
+    middle values for even n); n >= 2 k + 1 or a ValueError."""
+    t = C.check_trim_k(trim_k)
+    if t is None:
+        raise ValueError("trim_count: trim_k is not set")
+    return C.check_trim_sizes(n, t, "the round's clients")
+
+
+def fedavg_trimmed(global_state: torch.Tensor, finals: torch.Tensor, k_or_median, eta: float, dp: bool,
+                   sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
+    """In-place coordinate-wise trimmed mean of ``finals`` [n, S] (single rank): per coordinate of
+    the ``n_update`` leading entries the k smallest and k largest client values are dropped
+    (``ops.trimmed_delta_sum``: one fused HIP pass, the sort in registers) and ``w += (eta / (n -
+    2 k)) * total (+ noise)``.  Returns (kept share [n], high share [n]): the fraction of the
+    aggregated coordinates at which each client's value was kept / cut as too high."""
+    n = finals.shape[0]
+    k = trim_count(n, k_or_median)
+    total, kept, high = ops.trimmed_delta_sum(finals[:, :n_update], global_state[:n_update], k)
+    return trimmed_apply(global_state, total, kept, high, n, k, eta, dp, sigma, seed, n_update)
+
+
+def trimmed_apply(global_state: torch.Tensor, total: torch.Tensor, kept: torch.Tensor, high: torch.Tensor, n: int,
+                  k: int, eta: float, dp: bool, sigma: float, seed: int, n_update: int
+                  ) -> Tuple[List[float], List[float]]:
+    """``w += (eta / (n - 2 k)) * total (+ noise)`` from the fp64 trimmed sum; the counts as shares
+    of the ``n_update`` coordinates."""
+    ops.add_noise_scaled(global_state[:n_update], total, eta / (n - 2 * k), sigma, seed, dp)
+    den = float(max(1, n_update))
+    return [float(v) / den for v in kept.tolist()], [float(v) / den for v in high.tolist()]
 
 
 def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol: float, poll: int = 0):

@@ -215,10 +215,11 @@ class Server:
         if rounds <= 0:
             return
         p = self.params
-        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm", "krum_f", "krum_m")}
+        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm", "krum_f", "krum_m",
+                                    "trim_k")}
         # (plain FedAvg: the warm start stands in for a checkpoint trained without a defence)
         p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None,
-                  "krum_f": None, "krum_m": None})
+                  "krum_f": None, "krum_m": None, "trim_k": None})
         if lr is not None:
             p["lr"] = float(lr)
         try:
@@ -535,7 +536,7 @@ class Server:
         Client snapshots stay on their owner rank.  Only the rows some other rank reads are
         broadcast from their owners: the snapshots of clients whose tests are image-sharded across ranks
         (the round's longest clients, or every client without early local tests) and, for
-        RFA in gather mode and for Multi-Krum, the final states.  Aggregation itself reduces
+        RFA in gather mode, for Multi-Krum and for the trimmed mean, the final states.  Aggregation itself reduces
         (``_aggregate``)."""
         S, P = self.spec.S, self.spec.P
         world, rank = self.d.world, self.d.rank
@@ -560,8 +561,9 @@ class Server:
                 shared.update(plan.jobs[j].model for j in range(len(plan.jobs))
                               if j not in done_early and plan.jobs[j].model != 0)
             if ((self.params["aggregation_methods"] == C.AGGR_GEO_MED and self._rfa_gather(len(plan.clients)))
-                    or self.params.krum_f is not None):
-                # (Multi-Krum scores every client against every other: every rank needs every final row)
+                    or self.params.krum_f is not None or self.params.trim_k is not None):
+                # (Multi-Krum scores every client against every other, the trimmed mean sorts every
+                # coordinate over all clients: every rank needs every final row)
                 shared.update(c.final_snap for c in plan.clients)
             for s, t in local_snaps.items():
                 bank[s] = t
@@ -633,6 +635,8 @@ class Server:
             self._aggregate_clipped(plan, local, names, adversarial, p.clip_norm, n_upd, dp_seed)
         elif method == C.AGGR_MEAN and p.krum_f is not None:
             self._aggregate_krum(plan, bank, names, adversarial, p.krum_f, p.krum_m, n_upd, dp_seed)
+        elif method == C.AGGR_MEAN and p.trim_k is not None:
+            self._aggregate_trimmed(plan, bank, names, adversarial, p.trim_k, n_upd, dp_seed)
         elif method == C.AGGR_MEAN:
             # each rank sums its own clients' deltas (fp64), one all-reduce of S values
             part = ops.delta_sum(local["finals"][:, :n_upd], self.global_state[:n_upd])
@@ -746,6 +750,26 @@ class Server:
                  f"adversaries selected: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}")
         self.csv.add_weight_result(names, mask, sc)
         self._plot_weights(names, mask, sc, adversarial, plan.epoch)
+
+    def _aggregate_trimmed(self, plan: RoundPlan, bank: torch.Tensor, names: List[Any], adversarial: List[Any],
+                           trim_k: Any, n_upd: int, dp_seed: int) -> None:
+        """Coordinate-wise trimmed mean / median (``trim_k``) on the gathered final states:
+        ``_gather`` has broadcast every client's final row into every rank's bank, so every rank
+        runs the same fused pass over the bank rows in place (picked by their slots) and applies the
+        trimmed sum redundantly.  No collective follows the gather: the same rows in the same order
+        through the same kernel give every rank, at every world size, the same bits.  (Sharding the
+        coordinates over the ranks and all-gathering the totals would move fewer bytes.)"""
+        p = self.params
+        n = len(plan.clients)
+        k = agg.trim_count(n, trim_k)
+        slots = [c.final_snap for c in plan.clients]
+        total, kept, high = ops.trimmed_delta_sum(bank[:, :n_upd], self.global_state[:n_upd], k, slots)
+        ks, hs = agg.trimmed_apply(self.global_state, total, kept, high, n, k, float(p["eta"]),
+                                   bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
+        shares = ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, ks))
+        log.info(f"[trim agg] k: {k}  n: {n}  kept share (* adversary): {shares}")
+        self.csv.add_weight_result(names, ks, hs)
+        self._plot_weights(names, ks, hs, adversarial, plan.epoch)
 
     def _log_poison_ratio(self, tag: str, names: List[Any], ns: List[int]) -> None:
         p = self.params

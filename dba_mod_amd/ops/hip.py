@@ -69,6 +69,9 @@ _SIGS = {
     # Multi-Krum pairwise distances (csrc/kernels/krum.hip)
     "dba_pairwise_sqdist_blocks": [_LL],
     "dba_pairwise_sqdist": [_P, _LL, _P, _I, _LL, _P, _P, _P],
+    # coordinate-wise trimmed mean / median (csrc/kernels/trim.hip)
+    "dba_coord_trim_blocks": [_LL],
+    "dba_coord_trim": [_P, _LL, _P, _I, _P, _I, _LL, _P, _P, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
@@ -1409,6 +1412,45 @@ def pairwise_sq_dists(buf, row_idx=None):
     part = torch.empty(n * (n - 1) // 2 * nb, dtype=torch.float64, device=buf.device)
     _call("dba_pairwise_sqdist", buf.data_ptr(), rs, _ptr(idx), n, L, out.data_ptr(), part.data_ptr(), _stream())
     return out
+
+
+TRIM_MAX_ROWS = 64         # trim.hip kMaxRows
+
+
+def trimmed_delta_sum(buf, base, k, row_idx=None):
+    """(total fp64 [L], kept int64 [n], high int64 [n]) of the coordinate-wise trimmed sum of
+    ``buf[row] - base`` (trim.hip): one fused pass over the rows where they lie (``row_idx``: n row
+    numbers into ``buf``, repeats allowed), each coordinate sorted in registers, ranks k .. n - 1 - k
+    added in ascending order in fp64; no atomics, bitwise run to run.  More than 64 rows (or 2^31
+    coordinates) take the reference composition on the device."""
+    assert buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
+    assert base.dtype == torch.float32 and base.device == buf.device
+    if buf.shape[1] > 1 and buf.stride(1) != 1:
+        buf = buf.contiguous()
+    R, L = buf.shape
+    assert base.numel() == L, (tuple(buf.shape), base.numel())
+    idx = None
+    if row_idx is not None:
+        rows = [int(r) for r in (row_idx.tolist() if isinstance(row_idx, Tensor) else row_idx)]
+        if not all(0 <= r < R for r in rows):       # (the kernel reads rows[r] * stride unchecked)
+            raise ValueError(f"trimmed_delta_sum: row_idx {rows} outside the {R} rows of buf")
+        idx = torch.tensor(rows, dtype=torch.int32, device=buf.device)
+    n = R if idx is None else idx.numel()
+    k = _ref.check_trim(n, k)
+    if n > TRIM_MAX_ROWS or L >= 1 << 31:
+        return _ref.trimmed_delta_sum(buf, base, k, row_idx)
+    if n == 0 or L == 0:
+        return (torch.zeros(L, dtype=torch.float64, device=buf.device),
+                torch.zeros(n, dtype=torch.int64, device=buf.device),
+                torch.zeros(n, dtype=torch.int64, device=buf.device))
+    rs = buf.stride(0) if R > 1 else L
+    base = base.contiguous()
+    total = torch.empty(L, dtype=torch.float64, device=buf.device)
+    counts = torch.empty(n, 2, dtype=torch.int64, device=buf.device)
+    part = torch.empty(2 * n * int(_L.dba_coord_trim_blocks(L)), dtype=torch.int64, device=buf.device)
+    _call("dba_coord_trim", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), k, L, total.data_ptr(),
+          counts.data_ptr(), part.data_ptr(), _stream())
+    return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
 
 
 def gram(feats):

@@ -634,6 +634,57 @@ def pairwise_sq_dists(buf: Tensor, row_idx=None) -> Tensor:
     return D + D.t()
 
 
+TRIM_CHUNK = 1 << 18
+
+
+def check_trim(n: int, k: int) -> int:
+    """The trim count of n rows: an integer with 0 <= k and 2 k + 1 <= n (k = 0 when n = 0)."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0 or (2 * k + 1 > n and not (n == 0 and k == 0)):
+        raise ValueError(f"trimmed_delta_sum: k = {k!r} needs 0 <= k <= (n - 1) // 2 (n = {n})")
+    return k
+
+
+def trimmed_delta_sum(buf: Tensor, base: Tensor, k: int, row_idx=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Coordinate-wise trimmed sum of the client deltas (trimmed mean / median, Yin et al., ICML
+    2018; trim.hip is the GPU form): rows ``row_idx`` (n row numbers, repeats allowed) or all of
+    ``buf`` [R, L] fp32, ``base`` [L] fp32, ``0 <= k <= (n - 1) // 2``.  Per coordinate the n values
+    are sorted ascending (-inf first, +inf last among the numbers, every NaN after +inf, -0 == +0),
+    ``d_r = (double)s_r - (double)base`` and ``total = ((d_k + d_{k+1}) + ...) + d_{n-1-k}``, one
+    fp64 rounding per addition, in ascending rank.  With ``lo = s_k`` and ``hi = s_{n-1-k}``
+    (comparisons in which NaN compares false) a client is low at a coordinate if ``v < lo``, high
+    if ``v > hi`` or v is NaN and hi is not, kept otherwise; clients tied with a threshold are all
+    kept.  Returns (total fp64 [L], kept int64 [n], high int64 [n]): the coordinates each client
+    was kept / cut as high at (low is L - kept - high).  Chunked over L: no [n, L] fp64."""
+    assert buf.dim() == 2
+    idx = None
+    if row_idx is not None:
+        idx = torch.as_tensor(row_idx, dtype=torch.int64, device=buf.device).reshape(-1)
+    n = buf.shape[0] if idx is None else idx.numel()
+    L = buf.shape[1]
+    k = check_trim(n, k)
+    total = torch.zeros(L, dtype=torch.float64, device=buf.device)
+    kept = torch.zeros(n, dtype=torch.int64, device=buf.device)
+    high = torch.zeros(n, dtype=torch.int64, device=buf.device)
+    if n == 0:
+        return total, kept, high
+    b = base.double()
+    for c0 in range(0, L, TRIM_CHUNK):
+        x = buf[:, c0:c0 + TRIM_CHUNK]
+        x = x if idx is None else x.index_select(0, idx)
+        s = torch.sort(x, dim=0).values                       # (NaN last)
+        bc = b[c0:c0 + TRIM_CHUNK]
+        t = s[k].double() - bc
+        for r in range(k + 1, n - k):
+            t = t + (s[r].double() - bc)
+        total[c0:c0 + TRIM_CHUNK] = t
+        lo, hi = s[k][None], s[n - 1 - k][None]
+        is_low = x < lo
+        is_high = (x > hi) | (x.isnan() & ~hi.isnan())
+        kept += (~is_low & ~is_high).sum(1)
+        high += is_high.sum(1)
+    return total, kept, high
+
+
 def gram(feats: Tensor) -> Tensor:
     """F F^T in float64 (K15)."""
     f = feats.double()

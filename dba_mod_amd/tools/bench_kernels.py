@@ -70,6 +70,21 @@ def _time(fn, reps, inner=10):
     return e0.elapsed_time(e1) / (reps * inner) * 1e-3
 
 
+def _time_eager(fn, reps):
+    """GPU time per call of a torch composition that does not capture into a graph (``torch.sort``):
+    device events around ``reps`` eager calls; at milliseconds per call the host does not count."""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e-3
+
+
 def _bench_fp32(name, G, N, Hh, Cin, Cout, k, s, p, reps, dev):
     """fwd / dgrad / wgrad of the fp16-pair fp32 family; TFLOP/s counts the real fp32 work."""
     torch.manual_seed(0)
@@ -295,6 +310,52 @@ def _bench_krum(name, n, S, reps, dev):
             "fused_vs_composed_max_rel": rel}
 
 
+# coordinate-wise trimmed mean (trim.hip): a CIFAR round's 10 final states, k = 2 as in configs/cifar_trim.yaml
+TRIM = [("trim.cifar", 10, 2_802_430, 2)]
+
+
+def _bench_trim(name, n, S, k, reps, dev):
+    """The fused trimmed-sum kernel, reading the final-state rows where they lie in a snapshot
+    bank, against (a) the composition it replaces — the [n, S] copy of those rows, ``torch.sort``
+    along the clients, the fp64 deltas of the kept ranks and their sum (the same total bits; no
+    counts) — and (b) ``delta_sum`` over the same rows, plain FedAvg's pass: it moves the same
+    bytes and does no sorting, so it is the floor.  GB/s counts n * S * 4 bytes for all three."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    bank = base[None] + 0.01 * torch.randn(2 * n + 1, S, device=dev)      # finals in the odd slots
+    slots = torch.arange(1, 2 * n + 1, 2, device=dev)
+    rows = bank[1::2]                                                     # the same rows as a strided view
+    assert rows.shape[0] == n and torch.equal(rows, bank[slots])
+    bd = base.double()
+
+    def composed():
+        s = torch.sort(bank[slots], dim=0).values
+        return (s[k:n - k].double() - bd[None]).sum(0)
+
+    total, kept, high = H.trimmed_delta_sum(rows, base, k)
+    rt, rk, rh = R.trimmed_delta_sum(bank, base, k, slots)
+    assert torch.equal(total, rt) and torch.equal(kept, rk) and torch.equal(high, rh)
+    max_rel = float(((total - composed()).abs() / total.abs().clamp_min(1e-300)).max())
+    t_fused = _time(lambda: H.trimmed_delta_sum(rows, base, k), reps)
+    # (S is even but no multiple of 4: the bank's odd rows start 8 bytes off a 16-byte boundary
+    # and take the scalar-load path; a padded copy has every row aligned)
+    pad = torch.zeros(n, (S + 3) // 4 * 4, device=dev)
+    pad[:, :S] = rows
+    assert torch.equal(H.trimmed_delta_sum(pad[:, :S], base, k)[0], total)
+    t_aligned = _time(lambda: H.trimmed_delta_sum(pad[:, :S], base, k), reps)
+    t_comp = _time_eager(composed, reps)
+    t_ref = _time_eager(lambda: R.trimmed_delta_sum(bank, base, k, slots), reps)
+    t_dsum = _time(lambda: H.delta_sum(rows, base), reps)
+    b = n * S * 4
+    return {"shape": name, "n": n, "S": S, "k": k, "fused_us": round(t_fused * 1e6, 1),
+            "fused_GBps": round(b / t_fused / 1e9, 1), "fused_aligned_us": round(t_aligned * 1e6, 1),
+            "fused_aligned_GBps": round(b / t_aligned / 1e9, 1), "composed_us": round(t_comp * 1e6, 1),
+            "composed_GBps": round(b / t_comp / 1e9, 1), "reference_op_us": round(t_ref * 1e6, 1),
+            "delta_sum_us": round(t_dsum * 1e6, 1), "delta_sum_GBps": round(b / t_dsum / 1e9, 1),
+            "fused_vs_composed_max_rel": max_rel}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -327,6 +388,10 @@ def main(argv=None) -> int:
     for name, n, S in KRUM:
         if args.only in name:
             rows.append(_bench_krum(name, n, S, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, n, S, k in TRIM:
+        if args.only in name:
+            rows.append(_bench_trim(name, n, S, k, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
