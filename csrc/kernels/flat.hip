@@ -10,6 +10,7 @@
 //   * anomaly-evasion distance loss  a*CE + (1-a)*||w - w_g||  on the grouped replicas
 //     (helper.py:111-123, image_train.py:87-90, loan_train.py:114-117)
 #include "common.hpp"
+#include "noise.hpp"
 #include <algorithm>
 
 namespace {
@@ -27,12 +28,7 @@ template <typename U>
 __global__ void noise_add_kernel(float* __restrict__ dst, const U* __restrict__ upd, long long n, float coef,
                                  float sigma, uint32_t seed, int noise) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float u = (float)(upd[i] * (U)coef);
-    if (noise) {
-      const uint32_t c = (uint32_t)(i * 2);
-      const float u1 = uniform01(seed, c), u2 = uniform01(seed, c + 1);
-      u += sigma * sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-    }
+    const float u = noise_scaled_update<U>(upd[i], coef, sigma, seed, noise, i);
     dst[i] += u;
   }
 }

@@ -140,6 +140,11 @@ _DEFAULTS: Dict[str, Any] = {
     # averaged.  None = off; an integer k >= 1 (needs n >= 2 k + 1); "median" = k = (n - 1) // 2,
     # the coordinate-wise median (the mean of the two middle values for even n)
     "trim_k": None,
+    # robust learning rate (aggregation "mean" only; Ozdayi, Kantarcioglu and Gel, AAAI 2021): the
+    # server takes a sign vote per coordinate over the clients' updates and applies the averaged
+    # update with a negative rate where the vote's |sum| is below theta.  None = off; an integer
+    # theta with 1 <= theta <= no_models
+    "rlr_threshold": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -194,6 +199,14 @@ class Params(dict):
             if self.clip_norm is not None or f is not None:
                 raise ValueError("trim_k cannot be combined with clip_norm or krum_f")
             check_trim_sizes(int(self["no_models"]), t, "no_models")
+        r = self.rlr_threshold
+        if r is not None:
+            if self["aggregation_methods"] != AGGR_MEAN:
+                raise ValueError(f"rlr_threshold is an option of aggregation {AGGR_MEAN!r} "
+                                 f"(got {self['aggregation_methods']!r})")
+            if self.clip_norm is not None or f is not None or t is not None:
+                raise ValueError("rlr_threshold cannot be combined with clip_norm, krum_f or trim_k")
+            check_rlr_sizes(int(self["no_models"]), r, "no_models")
 
     @property
     def type(self) -> str:
@@ -218,6 +231,11 @@ class Params(dict):
     def trim_k(self) -> Any:
         """The checked ``trim_k``: None (off), k >= 1 or ``"median"``."""
         return check_trim_k(self.get("trim_k"))
+
+    @property
+    def rlr_threshold(self) -> Optional[int]:
+        """The checked ``rlr_threshold``: None (off) or theta >= 1."""
+        return check_rlr_threshold(self.get("rlr_threshold"))
 
     @property
     def adversary_list(self) -> List[Any]:
@@ -319,6 +337,23 @@ def check_trim_sizes(n: int, trim_k: Any, what: str = "n") -> int:
     if n < 1 or n < 2 * k + 1:
         raise ValueError(f"trim_k {trim_k} needs {what} >= 2 k + 1 = {2 * max(k, 0) + 1} (got {n})")
     return k
+
+
+def check_rlr_threshold(v: Any) -> Optional[int]:
+    """None or an integer theta >= 1 (a bool, a float, a string or a list is an error)."""
+    if v is None:
+        return None
+    if isinstance(v, int) and not isinstance(v, bool) and v >= 1:
+        return v
+    raise ValueError(f"rlr_threshold {v!r}: expected None or an integer >= 1")
+
+
+def check_rlr_sizes(n: int, theta: int, what: str = "n") -> int:
+    """The vote threshold for n clients: 1 <= theta <= n (|V| <= n, so a larger theta would flip
+    every coordinate)."""
+    if theta < 1 or theta > n:
+        raise ValueError(f"rlr_threshold {theta} needs 1 <= theta <= {what} (got {n})")
+    return theta
 
 
 def _same_client(a: Any, b: Any) -> bool:

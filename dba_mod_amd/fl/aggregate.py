@@ -27,6 +27,15 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   pass over the strided final states (``ops.trimmed_delta_sum``: each coordinate sorted in
   registers, the kept ranks added in ascending order in fp64, so every bit is fixed by IEEE
   arithmetic) also counts, per client, the coordinates at which it was kept or cut.
+* :func:`fedavg_rlr` / :func:`rlr_finish` / :func:`rlr_theta` — robust learning rate (config
+  ``rlr_threshold``; Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference): per coordinate
+  the signs of the clients' updates are summed and the averaged update is applied with a negative
+  rate wherever the vote's |sum| is below theta; magnitudes play no part.  The fp64 delta sum and the
+  int32 votes come from one fused HIP pass over the strided final states (``ops.delta_sum_votes``),
+  the per-client agreement counts from a second (``ops.vote_agreement``) and the signed update from
+  ``ops.rlr_apply`` (``add_noise_scaled``'s bits with ``+coef`` / ``-coef``).  Sums over clients
+  decompose, so the clients stay on their owner ranks and every quantity is an integer or an fp64
+  sum in client order.
 * :func:`geometric_median` / :func:`geometric_median_distributed` — RFA / Weiszfeld,
   ``helper.py:295-373`` (the latter with the points resident on their owner ranks): one batched distance
   kernel (all n clients in one pass) and one weighted-sum kernel per iteration; weights and
@@ -258,6 +267,43 @@ def trimmed_apply(global_state: torch.Tensor, total: torch.Tensor, kept: torch.T
     ops.add_noise_scaled(global_state[:n_update], total, eta / (n - 2 * k), sigma, seed, dp)
     den = float(max(1, n_update))
     return [float(v) / den for v in kept.tolist()], [float(v) / den for v in high.tolist()]
+
+
+def rlr_theta(n: int, theta) -> int:
+    """The vote threshold of a round of n clients: ``rlr_threshold`` itself, checked again against
+    the round's actual client count (1 <= theta <= n) or a ValueError."""
+    t = C.check_rlr_threshold(theta)
+    if t is None:
+        raise ValueError("rlr_theta: rlr_threshold is not set")
+    return C.check_rlr_sizes(n, t, "the round's clients")
+
+
+def fedavg_rlr(global_state: torch.Tensor, finals: torch.Tensor, theta: int, eta: float, no_models: int,
+               dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float], int]:
+    """In-place robust-learning-rate FedAvg of ``finals`` [n, S] (single rank): per coordinate of
+    the ``n_update`` leading entries the clients' signs are summed (``ops.delta_sum_votes``: one
+    fused HIP pass that also gives plain FedAvg's fp64 delta sum) and ``w += (eta / no_models) *
+    total (+ noise)`` where ``|V| >= theta``, ``w -= ...`` where it is not (``ops.rlr_apply``).  Returns
+    (agree share [n], dissent share [n], flipped): the fraction of the aggregated coordinates that
+    were kept and at which each client's non-zero sign agreed with / opposed the vote
+    (``ops.vote_agreement``, against the old ``w``), and the number of flipped coordinates."""
+    n = finals.shape[0]
+    theta = rlr_theta(n, theta)
+    rows, base = finals[:, :n_update], global_state[:n_update]
+    total, votes = ops.delta_sum_votes(rows, base)
+    counts = ops.vote_agreement(rows, base, votes, theta)
+    return rlr_finish(global_state, total, votes, counts, theta, eta, no_models, dp, sigma, seed, n_update)
+
+
+def rlr_finish(global_state: torch.Tensor, total: torch.Tensor, votes: torch.Tensor, counts: torch.Tensor,
+               theta: int, eta: float, no_models: int, dp: bool, sigma: float, seed: int, n_update: int
+               ) -> Tuple[List[float], List[float], int]:
+    """The robust-learning-rate update from the (all-reduced) fp64 delta sum, int32 votes and
+    [n, 2] int64 agreement counts; the counts as shares of the ``n_update`` coordinates."""
+    flipped = ops.rlr_apply(global_state[:n_update], total, votes, theta, eta / no_models, sigma, seed, dp)
+    den = float(max(1, n_update))
+    c = counts.cpu().tolist()
+    return [float(a) / den for a, _ in c], [float(d) / den for _, d in c], int(flipped)
 
 
 def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol: float, poll: int = 0):

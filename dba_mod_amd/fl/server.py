@@ -216,10 +216,10 @@ class Server:
             return
         p = self.params
         saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm", "krum_f", "krum_m",
-                                    "trim_k")}
+                                    "trim_k", "rlr_threshold")}
         # (plain FedAvg: the warm start stands in for a checkpoint trained without a defence)
         p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None,
-                  "krum_f": None, "krum_m": None, "trim_k": None})
+                  "krum_f": None, "krum_m": None, "trim_k": None, "rlr_threshold": None})
         if lr is not None:
             p["lr"] = float(lr)
         try:
@@ -637,6 +637,8 @@ class Server:
             self._aggregate_krum(plan, bank, names, adversarial, p.krum_f, p.krum_m, n_upd, dp_seed)
         elif method == C.AGGR_MEAN and p.trim_k is not None:
             self._aggregate_trimmed(plan, bank, names, adversarial, p.trim_k, n_upd, dp_seed)
+        elif method == C.AGGR_MEAN and p.rlr_threshold is not None:
+            self._aggregate_rlr(plan, local, names, adversarial, p.rlr_threshold, n_upd, dp_seed)
         elif method == C.AGGR_MEAN:
             # each rank sums its own clients' deltas (fp64), one all-reduce of S values
             part = ops.delta_sum(local["finals"][:, :n_upd], self.global_state[:n_upd])
@@ -770,6 +772,41 @@ class Server:
         log.info(f"[trim agg] k: {k}  n: {n}  kept share (* adversary): {shares}")
         self.csv.add_weight_result(names, ks, hs)
         self._plot_weights(names, ks, hs, adversarial, plan.epoch)
+
+    def _aggregate_rlr(self, plan: RoundPlan, local: Dict[str, Any], names: List[Any], adversarial: List[Any],
+                       rlr_threshold: int, n_upd: int, dp_seed: int) -> None:
+        """Robust learning rate (``rlr_threshold``) on rank-resident clients: sign sums and delta
+        sums decompose over clients, so every rank takes the fp64 delta sum and the int32 votes of
+        its own clients in one fused pass (zeros on a rank without clients); ONE all-reduce of the
+        fp64 total (the one plain FedAvg does) and ONE of the int32 votes (integer addition: exact);
+        every rank then counts its own clients' agreement with the reduced votes, against the old
+        global state; ONE all-reduce of the [n, 2] int64 counts (each row owned by one rank, zero
+        elsewhere); every rank applies the signed update redundantly.  No final state is broadcast."""
+        p = self.params
+        n = len(plan.clients)
+        theta = agg.rlr_theta(n, rlr_threshold)
+        idx = local["idx"]
+        rows, base = local["finals"][:, :n_upd], self.global_state[:n_upd]
+        if idx:
+            total, votes = ops.delta_sum_votes(rows, base)
+        else:
+            total = torch.zeros(n_upd, dtype=torch.float64, device=self.device)
+            votes = torch.zeros(n_upd, dtype=torch.int32, device=self.device)
+        total = self._reduce(total)
+        votes = self._reduce(votes)
+        counts = torch.zeros(n, 2, dtype=torch.int64, device=self.device)
+        if idx:
+            counts[torch.tensor(idx, dtype=torch.int64, device=self.device)] = ops.vote_agreement(rows, base, votes,
+                                                                                                  theta)
+        counts = self._reduce(counts)
+        ag, ds, flipped = agg.rlr_finish(self.global_state, total, votes, counts, theta, float(p["eta"]),
+                                         int(p["no_models"]), bool(p["diff_privacy"]), float(p["sigma"]), dp_seed,
+                                         n_upd)
+        shares = ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, ag))
+        log.info(f"[rlr agg] theta: {theta}  n: {n}  flipped: {flipped}/{n_upd} ({flipped / max(1, n_upd):.4f})  "
+                 f"agree share (* adversary): {shares}")
+        self.csv.add_weight_result(names, ag, ds)
+        self._plot_weights(names, ag, ds, adversarial, plan.epoch)
 
     def _log_poison_ratio(self, tag: str, names: List[Any], ns: List[int]) -> None:
         p = self.params

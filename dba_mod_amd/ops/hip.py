@@ -72,6 +72,12 @@ _SIGS = {
     # coordinate-wise trimmed mean / median (csrc/kernels/trim.hip)
     "dba_coord_trim_blocks": [_LL],
     "dba_coord_trim": [_P, _LL, _P, _I, _P, _I, _LL, _P, _P, _P, _P],
+    # robust-learning-rate FedAvg: sign votes (csrc/kernels/rlr.hip)
+    "dba_vote_agreement_blocks": [_LL],
+    "dba_rlr_apply_blocks": [_LL],
+    "dba_delta_sum_votes": [_P, _LL, _I, _P, _LL, _P, _P, _P],
+    "dba_vote_agreement": [_P, _LL, _I, _P, _P, _I, _LL, _P, _P, _P],
+    "dba_rlr_apply": [_P, _P, _P, _I, _LL, _F, _F, _U, _I, _P, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
@@ -1451,6 +1457,72 @@ def trimmed_delta_sum(buf, base, k, row_idx=None):
     _call("dba_coord_trim", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), k, L, total.data_ptr(),
           counts.data_ptr(), part.data_ptr(), _stream())
     return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
+
+
+RLR_MAX_ROWS = 65535       # rlr.hip kMaxGridY: the agreement pass takes one grid row per client
+
+
+def _rlr_theta(theta) -> int:
+    theta = int(theta)
+    if not -(1 << 31) <= theta < (1 << 31):
+        raise ValueError(f"rlr: theta {theta} does not fit an int32")
+    return theta
+
+
+def delta_sum_votes(rows, base):
+    """(total fp64 [L], votes int32 [L]): the FedAvg delta sum in row order (the bits of
+    ``delta_sum``) and the per-coordinate sign vote, in one fused pass over the strided rows
+    (rlr.hip delta_sum_votes_kernel); any number of rows."""
+    rows, rs, base = _delta_rows(rows, base)
+    n, L = rows.shape
+    if n == 0 or L == 0:
+        return (torch.zeros(L, dtype=torch.float64, device=base.device),
+                torch.zeros(L, dtype=torch.int32, device=base.device))
+    total = torch.empty(L, dtype=torch.float64, device=base.device)
+    votes = torch.empty(L, dtype=torch.int32, device=base.device)
+    _call("dba_delta_sum_votes", rows.data_ptr(), rs, n, base.data_ptr(), L, total.data_ptr(), votes.data_ptr(),
+          _stream())
+    return total, votes
+
+
+def vote_agreement(rows, base, votes, theta):
+    """int64 [n, 2] (agree, dissent) of each strided row against the reduced votes at threshold
+    ``theta`` (rlr.hip vote_agreement_kernel): per-block integer partials finalised in a fixed
+    order, no atomics, bitwise run to run."""
+    rows, rs, base = _delta_rows(rows, base)
+    n, L = rows.shape
+    theta = _rlr_theta(theta)
+    assert votes.dtype == torch.int32 and votes.numel() == L and votes.device == base.device
+    if n == 0 or L == 0:
+        return torch.zeros(n, 2, dtype=torch.int64, device=base.device)
+    if n > RLR_MAX_ROWS:
+        return torch.cat([vote_agreement(rows[i:i + RLR_MAX_ROWS], base, votes, theta)
+                          for i in range(0, n, RLR_MAX_ROWS)])
+    votes = votes.reshape(-1).contiguous()
+    counts = torch.empty(n, 2, dtype=torch.int64, device=base.device)
+    part = torch.empty(2 * n * int(_L.dba_vote_agreement_blocks(L)), dtype=torch.int64, device=base.device)
+    _call("dba_vote_agreement", rows.data_ptr(), rs, n, base.data_ptr(), votes.data_ptr(), theta, L,
+          counts.data_ptr(), part.data_ptr(), _stream())
+    return counts
+
+
+def rlr_apply(dst, total, votes, theta, coef, sigma, seed, noise):
+    """``dst += (float)(total * (double)(|votes| >= theta ? coef : -coef)) (+ noise)`` in place (rlr.hip
+    rlr_apply_kernel: the update of ``add_noise_scaled``, bit for bit, with ``-coef`` at the flipped
+    coordinates); returns the number of flipped coordinates as an int64 scalar on the device."""
+    assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.dim() == 1 and dst.is_cuda
+    L = dst.numel()
+    theta = _rlr_theta(theta)
+    assert total.dtype == torch.float64 and total.numel() == L and total.device == dst.device
+    assert votes.dtype == torch.int32 and votes.numel() == L and votes.device == dst.device
+    if L == 0:
+        return torch.zeros((), dtype=torch.int64, device=dst.device)
+    flipped = torch.empty((), dtype=torch.int64, device=dst.device)
+    total, votes = total.reshape(-1).contiguous(), votes.reshape(-1).contiguous()
+    part = torch.empty(int(_L.dba_rlr_apply_blocks(L)), dtype=torch.int64, device=dst.device)
+    _call("dba_rlr_apply", dst.data_ptr(), total.data_ptr(), votes.data_ptr(), theta, L, float(coef), float(sigma),
+          int(seed) & 0xFFFFFFFF, int(bool(noise)), flipped.data_ptr(), part.data_ptr(), _stream())
+    return flipped
 
 
 def gram(feats):

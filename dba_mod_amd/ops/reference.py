@@ -685,6 +685,83 @@ def trimmed_delta_sum(buf: Tensor, base: Tensor, k: int, row_idx=None) -> Tuple[
     return total, kept, high
 
 
+RLR_CHUNK = 1 << 18
+
+
+def _rlr_rows(rows: Tensor, base: Tensor) -> Tuple[int, int]:
+    assert rows.dim() == 2 and rows.dtype == torch.float32 and base.dtype == torch.float32
+    assert rows.shape[1] == base.numel(), (tuple(rows.shape), base.numel())
+    return rows.shape[0], rows.shape[1]
+
+
+def delta_sum_votes(rows: Tensor, base: Tensor) -> Tuple[Tensor, Tensor]:
+    """(total fp64 [L], votes int32 [L]) of the robust learning rate's sign vote (rlr.hip is the GPU
+    form): ``total = sum_i ((double)rows_i - (double)base)`` added in row order, one fp64 rounding
+    per addition (the bits of :func:`delta_sum`), and ``votes = sum_i s_i`` with ``s_i`` = +1 where
+    ``rows_i > base``, -1 where ``rows_i < base``, 0 otherwise: fp32 comparisons, so a NaN on either
+    side and -0 against +0 vote 0 (a non-finite value still enters ``total``).  Chunked over L: no
+    full [n, L] temporary."""
+    n, L = _rlr_rows(rows, base)
+    total = torch.zeros(L, dtype=torch.float64, device=base.device)
+    votes = torch.zeros(L, dtype=torch.int32, device=base.device)
+    for c0 in range(0, L if n else 0, RLR_CHUNK):
+        b = base[c0:c0 + RLR_CHUNK]
+        bd = b.double()
+        t = total[c0:c0 + RLR_CHUNK]
+        v = votes[c0:c0 + RLR_CHUNK]
+        for i in range(n):
+            x = rows[i, c0:c0 + RLR_CHUNK]
+            t += x.double() - bd
+            v += (x > b).to(torch.int32) - (x < b).to(torch.int32)
+    return total, votes
+
+
+def vote_agreement(rows: Tensor, base: Tensor, votes: Tensor, theta: int) -> Tensor:
+    """int64 [n, 2] (agree, dissent) of each row against the reduced ``votes`` [L] at threshold
+    ``theta``: over the kept coordinates (``|votes| >= theta``) only, with ``m = sign(votes)``, the
+    coordinates at which the row's sign (as in :func:`delta_sum_votes`) is non-zero and equals m /
+    equals -m.  Chunked over L."""
+    n, L = _rlr_rows(rows, base)
+    assert votes.numel() == L
+    votes = votes.reshape(-1)
+    counts = torch.zeros(n, 2, dtype=torch.int64, device=base.device)
+    for c0 in range(0, L if n else 0, RLR_CHUNK):
+        b = base[c0:c0 + RLR_CHUNK][None]
+        x = rows[:, c0:c0 + RLR_CHUNK]
+        V = votes[c0:c0 + RLR_CHUNK].to(torch.int64)
+        s = (x > b).to(torch.int64) - (x < b).to(torch.int64)
+        m = torch.sign(V)[None]
+        live = ((V.abs() >= int(theta))[None]) & (s != 0)
+        counts[:, 0] += (live & (s == m)).sum(1)
+        counts[:, 1] += (live & (s == -m)).sum(1)
+    return counts
+
+
+def rlr_apply(dst: Tensor, total: Tensor, votes: Tensor, theta: int, coef: float, sigma: float, seed: int,
+              noise: bool) -> Tensor:
+    """The robust-learning-rate update, in place: ``dst += (float)(total * (double)(kept ? coef :
+    -coef))`` (+ N(0, sigma) per element if ``noise``: the hash RNG and counters of
+    :func:`add_noise_scaled`) with ``kept = |votes| >= theta``; a kept coordinate gets the bits of
+    :func:`add_noise_scaled` with ``coef``, a flipped one those with ``-coef``.  ``total`` fp64 [L],
+    ``votes`` int32 [L].  Returns the number of flipped coordinates (an int64 scalar tensor).
+    Chunked over L."""
+    L = dst.numel()
+    assert dst.dim() == 1 and total.numel() == L and votes.numel() == L and total.dtype == torch.float64
+    total, votes = total.reshape(-1), votes.reshape(-1)
+    flipped = torch.zeros((), dtype=torch.int64, device=dst.device)
+    cpos = torch.tensor(float(coef), dtype=torch.float64, device=dst.device)     # (as add_noise_scaled multiplies)
+    for c0 in range(0, L, RLR_CHUNK):
+        t = total[c0:c0 + RLR_CHUNK]
+        kept = votes[c0:c0 + RLR_CHUNK].to(torch.int64).abs() >= int(theta)
+        u = (t * torch.where(kept, cpos, -cpos)).to(dst.dtype)
+        if noise:
+            ctr = torch.arange(c0, c0 + u.numel(), dtype=torch.int64, device=u.device)
+            u = u + sigma * rng.normal(seed, ctr)
+        dst[c0:c0 + RLR_CHUNK] += u
+        flipped += (~kept).sum()
+    return flipped
+
+
 def gram(feats: Tensor) -> Tensor:
     """F F^T in float64 (K15)."""
     f = feats.double()

@@ -356,6 +356,65 @@ def _bench_trim(name, n, S, k, reps, dev):
             "fused_vs_composed_max_rel": max_rel}
 
 
+# robust learning rate (rlr.hip): a CIFAR round's 10 final states, theta = 4 as in configs/cifar_rlr.yaml
+RLR = [("rlr.cifar", 10, 2_802_430, 4)]
+
+
+def _bench_rlr(name, n, S, theta, reps, dev):
+    """The three fused passes, reading the final states as the server holds them (the stacked
+    [n, S] rows: S is even but no multiple of 4, so every odd row starts 8 bytes off a 16-byte
+    boundary), each against the ``ops.reference`` composition on the same device (chunked torch
+    ops, timed eagerly) and checked to give its bits.  The sum + votes pass must move n * S * 4
+    (rows) + S * 4 (base) + S * 12 (fp64 total and int32 votes out) bytes: GB/s counts those; the
+    agreement pass reads every row again with the base and the votes, the apply pass moves S * 20
+    bytes."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    finals = base[None] + 0.01 * torch.randn(n, S, device=dev)
+    finals[0] = base + 100.0 * (finals[0] - base)                 # a model-replacement client
+    finals[:, ::7] = base[::7]                                    # exact-zero deltas: abstentions
+    coef, sigma, seed = 0.1 / n, 0.01, 12345
+    total, votes = H.delta_sum_votes(finals, base)
+    rt, rv = R.delta_sum_votes(finals, base)
+    assert torch.equal(total, rt) and torch.equal(votes, rv) and torch.equal(total, H.delta_sum(finals, base))
+    counts = H.vote_agreement(finals, base, votes, theta)
+    assert torch.equal(counts, R.vote_agreement(finals, base, votes, theta))
+    out = {"shape": name, "n": n, "S": S, "theta": theta}
+    for noise in (False, True):
+        a, b, c = base.clone(), base.clone(), base.clone()
+        fa = H.rlr_apply(a, total, votes, theta, coef, sigma, seed, noise)
+        H.add_noise_scaled(b, total, coef, sigma, seed, noise)
+        H.add_noise_scaled(c, total, -coef, sigma, seed, noise)
+        kept = votes.abs() >= theta
+        assert torch.equal(a, torch.where(kept, b, c)) and int(fa) == int((~kept).sum())
+    out["flipped_share"] = round(int(fa) / S, 4)
+    dst = base.clone()
+    t_votes = _time(lambda: H.delta_sum_votes(finals, base), reps)
+    t_dsum = _time(lambda: H.delta_sum(finals, base), reps)
+    t_agree = _time(lambda: H.vote_agreement(finals, base, votes, theta), reps)
+    t_apply = _time(lambda: H.rlr_apply(dst, total, votes, theta, coef, sigma, seed, False), reps)
+    t_apply_n = _time(lambda: H.rlr_apply(dst, total, votes, theta, coef, sigma, seed, True), reps)
+    t_noise = _time(lambda: H.add_noise_scaled(dst, total, coef, sigma, seed, False), reps)
+    r_votes = _time_eager(lambda: R.delta_sum_votes(finals, base), reps)
+    r_agree = _time_eager(lambda: R.vote_agreement(finals, base, votes, theta), reps)
+    r_apply = _time_eager(lambda: R.rlr_apply(dst, total, votes, theta, coef, sigma, seed, False), reps)
+    r_apply_n = _time_eager(lambda: R.rlr_apply(dst, total, votes, theta, coef, sigma, seed, True), reps)
+    b_votes = n * S * 4 + S * 4 + S * 12
+    b_agree = n * S * 4 + S * 8
+    out.update({"sum_votes_us": round(t_votes * 1e6, 1), "sum_votes_GBps": round(b_votes / t_votes / 1e9, 1),
+                "sum_votes_composed_us": round(r_votes * 1e6, 1),
+                "delta_sum_us": round(t_dsum * 1e6, 1),
+                "delta_sum_GBps": round((n * S * 4 + S * 12) / t_dsum / 1e9, 1),
+                "agreement_us": round(t_agree * 1e6, 1), "agreement_GBps": round(b_agree / t_agree / 1e9, 1),
+                "agreement_composed_us": round(r_agree * 1e6, 1),
+                "apply_us": round(t_apply * 1e6, 1), "apply_GBps": round(S * 20 / t_apply / 1e9, 1),
+                "apply_composed_us": round(r_apply * 1e6, 1),
+                "apply_noise_us": round(t_apply_n * 1e6, 1), "apply_noise_composed_us": round(r_apply_n * 1e6, 1),
+                "add_noise_scaled_us": round(t_noise * 1e6, 1)})
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -392,6 +451,10 @@ def main(argv=None) -> int:
     for name, n, S, k in TRIM:
         if args.only in name:
             rows.append(_bench_trim(name, n, S, k, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, n, S, theta in RLR:
+        if args.only in name:
+            rows.append(_bench_rlr(name, n, S, theta, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
