@@ -7,10 +7,10 @@
 //                        flat.hip wsum_fixed_kernel: exact and order-free, so rank partials
 //                        all-reduce to world-invariant bits), or in plain fp64 when the grid cannot
 //                        hold the sum (a non-finite delta, more than 512 clients)
-// Rows are read four floats per lane: one 16-byte load where the row start is 16-byte aligned,
-// four scalar loads otherwise (finals[:, :n_upd] is a strided view whose rows may start anywhere;
-// the compiler is free to serve the four as one dword-aligned wide load, which gfx950 allows).
+// Rows are read four floats per lane (rowquad.hpp; where a row start is not 16-byte aligned the
+// compiler is free to serve the four scalar loads as one dword-aligned wide load, which gfx950 allows).
 #include "common.hpp"
+#include "rowquad.hpp"
 #include <algorithm>
 #include <math.h>
 
@@ -20,32 +20,14 @@
 
 namespace {
 
-constexpr int kQuad = 4;           // floats per lane per step
 constexpr int kStatBlocksMax = 512;
 constexpr int kStatBatch = 4;      // quads in flight per lane in the stats pass
 constexpr int kSumBlocksMax = 4096;   // x 256 threads x 4 floats = 16384 * 256 elements per sweep
 
-__device__ __forceinline__ bool aligned16_dev(const float* p) { return ((uintptr_t)p & 15) == 0; }
-
-// four floats at p: one 16-byte load if ``vec`` (p 16-byte aligned), four scalar loads otherwise
-__device__ __forceinline__ void ld4(const float* __restrict__ p, bool vec, float (&v)[kQuad]) {
-  if (vec) {
-    const float4 x = *(const float4*)p;
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  } else {
-    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-  }
-}
-
-// floats p[0 .. cnt) (cnt = 4 except at the end of a row), zero-filled; a quad's offset from its
-// row start is a multiple of 16 bytes, so ``vec`` is the row start's alignment
-__device__ __forceinline__ void ld_quad(const float* __restrict__ p, bool vec, int cnt, float (&v)[kQuad]) {
-  if (cnt == kQuad) {
-    ld4(p, vec, v);
-  } else {
-#pragma unroll
-    for (int j = 0; j < kQuad; ++j) v[j] = j < cnt ? p[j] : 0.f;
-  }
+// floats p[0 .. cnt) (cnt = 4 except at the end of a row, tested at run time), zero-filled
+__device__ __forceinline__ void ld_row_quad(const float* __restrict__ p, bool vec, int cnt, float (&v)[kQuad]) {
+  if (cnt == kQuad) ld_quad_f4<true>(p, vec, kQuad, v);
+  else ld_quad_f4<false>(p, vec, cnt, v);
 }
 
 // one element of a client's delta into its thread's running sum of squares and max |.|
@@ -80,8 +62,8 @@ __global__ __launch_bounds__(256) void delta_stats_kernel(const float* __restric
     float x[kStatBatch][kQuad], b[kStatBatch][kQuad];
 #pragma unroll
     for (int u = 0; u < kStatBatch; ++u) {
-      ld4(p + (q + u * stride) * kQuad, vp, x[u]);
-      ld4(base + (q + u * stride) * kQuad, vb, b[u]);
+      ld_quad_f4<true>(p + (q + u * stride) * kQuad, vp, kQuad, x[u]);
+      ld_quad_f4<true>(base + (q + u * stride) * kQuad, vb, kQuad, b[u]);
     }
 #pragma unroll
     for (int u = 0; u < kStatBatch; ++u)
@@ -92,8 +74,8 @@ __global__ __launch_bounds__(256) void delta_stats_kernel(const float* __restric
     const long long k = q * kQuad;
     const int cnt = n - k < kQuad ? (int)(n - k) : kQuad;
     float x[kQuad], b[kQuad];
-    ld_quad(p + k, vp, cnt, x);
-    ld_quad(base + k, vb, cnt, b);
+    ld_row_quad(p + k, vp, cnt, x);
+    ld_row_quad(base + k, vb, cnt, b);
 #pragma unroll
     for (int j = 0; j < kQuad; ++j) stat_acc(x[j], b[j], s, m);   // (the zero fill adds 0 and leaves the max)
   }
@@ -153,13 +135,13 @@ __global__ __launch_bounds__(256) void clipped_sum_kernel(const float* __restric
     const long long k = q * kQuad;
     const int cnt = n - k < kQuad ? (int)(n - k) : kQuad;
     float b[kQuad];
-    ld_quad(base + k, vb, cnt, b);
+    ld_row_quad(base + k, vb, cnt, b);
     long long hs[kQuad] = {0, 0, 0, 0}, ls[kQuad] = {0, 0, 0, 0};
     double fs[kQuad] = {0.0, 0.0, 0.0, 0.0};
     for (int r = 0; r < nrows; ++r) {
       float x[kQuad];
       const float* p = rows + (long long)r * rstride;
-      ld_quad(p + k, aligned16_dev(p), cnt, x);
+      ld_row_quad(p + k, aligned16_dev(p), cnt, x);
       const double s = (double)scale[r];
 #pragma unroll
       for (int j = 0; j < kQuad; ++j) {

@@ -10,6 +10,7 @@
 //   * anomaly-evasion distance loss  a*CE + (1-a)*||w - w_g||  on the grouped replicas
 //     (helper.py:111-123, image_train.py:87-90, loan_train.py:114-117)
 #include "common.hpp"
+#include "rowquad.hpp"
 #include "noise.hpp"
 #include <algorithm>
 
@@ -59,11 +60,8 @@ __global__ __launch_bounds__(256) void sqdist_kernel(const float* __restrict__ p
     const double d = (double)p[k] - (double)m[k];
     s += d * d;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(long long)i * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) part[(long long)i * gridDim.x + blockIdx.x] = s;
 }
 
 __global__ void sqdist_finalize(const double* __restrict__ part, int nblk, int npts, double* __restrict__ out) {

@@ -16,9 +16,9 @@
 //     launch grid (quad q of every row goes to thread q mod the grid, in ascending q), not on the
 //     rows' alignment, on the tile a pair falls into or on the other rows of the call: the same
 //     bits from an aligned copy and a misaligned view, and from any subset of the rows
-// Rows are read four floats per lane as in clip.hip: one 16-byte load where the row start is
-// 16-byte aligned, four scalar loads otherwise.
+// Rows are read four floats per lane (rowquad.hpp).
 #include "common.hpp"
+#include "rowquad.hpp"
 #include <algorithm>
 #include <math.h>
 
@@ -27,7 +27,6 @@
 
 namespace {
 
-constexpr int kQuad = 4;            // floats per lane per step
 constexpr int kTile = 8;            // rows per tile: kTile x kTile fp64 accumulators per thread
 constexpr int kLone = 11;           // most rows of a lone triangular tile: 11 * 10 / 2 = 55 accumulators
 constexpr int kAcc = kTile * kTile;
@@ -35,26 +34,6 @@ constexpr int kMaxRows = 64;
 constexpr int kBlocksMax = 512;     // x 256 threads x 4 floats = 524288 elements per sweep of the grid
 
 static_assert(kLone * (kLone - 1) / 2 <= kAcc && kLone >= kTile, "a triangular tile's pairs fit the accumulators");
-
-__device__ __forceinline__ bool aligned16_dev(const float* p) { return ((uintptr_t)p & 15) == 0; }
-
-// a quad of a row: FULL, four floats at p in one 16-byte load if ``vec`` (a quad's offset from its
-// row start is a multiple of 16 bytes, so ``vec`` is the row start's alignment) or four scalar
-// loads otherwise; else the row's last floats p[0 .. cnt), cnt < 4, zero-filled
-template <bool FULL>
-__device__ __forceinline__ void ld_quad(const float* __restrict__ p, bool vec, int cnt, float (&v)[kQuad]) {
-  if constexpr (FULL) {
-    if (vec) {
-      const float4 x = *(const float4*)p;
-      v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    } else {
-      v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kQuad; ++j) v[j] = j < cnt ? p[j] : 0.f;
-  }
-}
 
 // the accumulator of local rows (a, b): a triangular (DIAG) tile holds its pairs a < b column by
 // column, an off-diagonal tile pair all kTile x kTile
@@ -118,7 +97,7 @@ template <bool FULL, int R>
 __device__ __forceinline__ void load_rows(const Rows<R>& t, long long k, int cnt, float (&x)[R][kQuad]) {
 #pragma unroll
   for (int r = 0; r < R; ++r)
-    if (r < t.n) ld_quad<FULL>(t.p[r] + k, t.vec[r], cnt, x[r]);
+    if (r < t.n) ld_quad_f4<FULL>(t.p[r] + k, t.vec[r], cnt, x[r]);
 }
 
 template <bool DIAG, bool FULL, int RA, int RB>
@@ -134,7 +113,7 @@ __device__ __forceinline__ void pair_step(const Rows<RA>& ta, const Rows<RB>& tb
       float xb[kBPart][kQuad];
 #pragma unroll
       for (int r = 0; r < kBPart; ++r)
-        if (h + r < tb.n) ld_quad<FULL>(tb.p[h + r] + k, tb.vec[h + r], cnt, xb[r]);
+        if (h + r < tb.n) ld_quad_f4<FULL>(tb.p[h + r] + k, tb.vec[h + r], cnt, xb[r]);
       pair_acc<false>(xa, xb, ta.n, tb.n, h, acc);
     }
   }

@@ -13,21 +13,19 @@
 //                         coordinate gets the bits of dba_add_noise_scaled with +coef / -coef; and
 //                         the number of flipped coordinates
 // Sums over clients decompose, so each rank runs the first two passes on its own rows and the
-// fp64 totals, int32 votes and int64 counts are all-reduced (Server._aggregate_rlr).
+// fp64 totals, int32 votes and int64 counts are all-reduced (fl/aggregate.py fedavg_rlr).
 // No atomics: the counts go through lanes in a fixed butterfly, the four waves in order, per-block
 // int64 partials and a finalize launch, so they are bitwise run to run; every other output
 // depends on its own coordinate alone, never on the launch grid.
-// Rows are read as in clip.hip / trim.hip: four floats per lane, one 16-byte load where the row
-// start is 16-byte aligned, four scalar loads otherwise (finals[:, :n_upd] is a strided view whose
-// rows may start anywhere); the last, partial step reads only the row's remaining floats and
-// stores only their results.  Outputs take 16-byte stores where their own start allows.
+// Rows are read four floats per lane (rowquad.hpp); outputs take 16-byte stores where their own
+// start allows.
 #include "common.hpp"
 #include "noise.hpp"
+#include "rowquad.hpp"
 #include <algorithm>
 
 namespace {
 
-constexpr int kQuad = 4;           // coordinates per lane per step
 constexpr int kBlocksMax = 4096;   // sum + votes, apply: x 256 threads x 4 coordinates = 4194304 per sweep
 constexpr int kRowBatch = 4;       // rows whose loads are in flight together in the sum + votes pass
 constexpr int kAgreeBatch = 4;     // quads in flight per lane in the agreement pass
@@ -35,76 +33,8 @@ constexpr int kAgreeBlocksMax = 1024;   // x 256 threads x kAgreeBatch x 4 coord
 constexpr int kFinalBatch = 4;     // partials in flight per thread in the finalize launch
 constexpr int kMaxGridY = 65535;
 
-__device__ __forceinline__ bool aligned16_dev(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// T p[0 .. 4) (FULL) or p[0 .. cnt), zero-filled; ``vec``: p is 16-byte aligned.  A quad's offset
-// from its row start is a multiple of 16 bytes, so ``vec`` is the row start's alignment
-template <bool FULL, typename T>
-__device__ __forceinline__ void ld_quad(const T* __restrict__ p, bool vec, int cnt, T (&v)[kQuad]) {
-  static_assert(sizeof(T) == 4, "four 4-byte elements per 16-byte load");
-  if constexpr (FULL) {
-    if (vec) {
-      const uint4 x = *(const uint4*)p;
-      __builtin_memcpy(v, &x, sizeof(x));
-    } else {
-      v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kQuad; ++j) v[j] = j < cnt ? p[j] : T(0);
-  }
-}
-
-// p[0 .. 4) (FULL) or p[0 .. cnt) = v
-template <bool FULL>
-__device__ __forceinline__ void st_quad(float* __restrict__ p, bool vec, int cnt, const float (&v)[kQuad]) {
-  if constexpr (FULL) {
-    if (vec) {
-      *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kQuad; ++j)
-    if (FULL || j < cnt) p[j] = v[j];
-}
-template <bool FULL>
-__device__ __forceinline__ void st_quad(int* __restrict__ p, bool vec, int cnt, const int (&v)[kQuad]) {
-  if constexpr (FULL) {
-    if (vec) {
-      *(int4*)p = make_int4(v[0], v[1], v[2], v[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kQuad; ++j)
-    if (FULL || j < cnt) p[j] = v[j];
-}
-template <bool FULL>
-__device__ __forceinline__ void st_quad(double* __restrict__ p, bool vec, int cnt, const double (&v)[kQuad]) {
-  if constexpr (FULL) {
-    if (vec) {
-      ((double2*)p)[0] = make_double2(v[0], v[1]);
-      ((double2*)p)[1] = make_double2(v[2], v[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kQuad; ++j)
-    if (FULL || j < cnt) p[j] = v[j];
-}
-
 // +1 / -1 / 0: fp32 comparisons (NaN on either side and -0 against +0 give 0)
 __device__ __forceinline__ int sign_of(float x, float b) { return (int)(x > b) - (int)(x < b); }
-
-// a block's count: lanes in a fixed butterfly, then the four waves in order (every thread calls it)
-__device__ __forceinline__ long long block_count(long long v, long long (&red)[4]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // ---------------------------------------------------------------------------------- apply
 // (compiled under the translation unit's default fp contraction, as flat.hip is: the update is
@@ -155,7 +85,7 @@ __global__ __launch_bounds__(256) void rlr_apply_kernel(float* __restrict__ dst,
   if (q < nq)
     flipped += apply_step<false>(dst, vd, total, vt, votes, vv, theta, q * kQuad, (int)(L - q * kQuad), coef, sigma,
                                  seed, noise);
-  const long long s = block_count(flipped, red);
+  const long long s = block_sum<long long>(flipped, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -275,7 +205,7 @@ __global__ __launch_bounds__(256) void vote_agreement_kernel(const float* __rest
     }
     agree_acc(x, b, V, theta, agree, dissent);
   }
-  const long long a = block_count(agree, red_a), d = block_count(dissent, red_d);
+  const long long a = block_sum<long long>(agree, red_a), d = block_sum<long long>(dissent, red_d);
   if (threadIdx.x == 0) {
     part[((long long)i * 2 + 0) * gridDim.x + blockIdx.x] = a;
     part[((long long)i * 2 + 1) * gridDim.x + blockIdx.x] = d;
@@ -284,7 +214,7 @@ __global__ __launch_bounds__(256) void vote_agreement_kernel(const float* __rest
 
 // one block per output slot: thread t takes the partials of blocks t, t + 256, ... (kFinalBatch
 // loads in flight: a chain of dependent L2 round trips over thousands of partials would take
-// longer than the pass over the rows), then the block combines in the fixed order of block_count
+// longer than the pass over the rows), then the block combines in the fixed order of block_sum
 __global__ __launch_bounds__(256) void count_finalize(const long long* __restrict__ part, int nblk,
                                                      long long* __restrict__ counts) {
   __shared__ long long red[4];
@@ -299,7 +229,7 @@ __global__ __launch_bounds__(256) void count_finalize(const long long* __restric
     for (int u = 0; u < kFinalBatch; ++u) s += v[u];
   }
   for (; b < nblk; b += 256) s += p[b];
-  s = block_count(s, red);
+  s = block_sum<long long>(s, red);
   if (threadIdx.x == 0) counts[blockIdx.x] = s;
 }
 

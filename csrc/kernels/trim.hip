@@ -22,10 +22,12 @@
 //     counters (kept in the low half of an int, high in the upper half; a thread takes fewer than
 //     2^16 coordinates for any L < 2^31) go through lanes in a butterfly, the four waves in order,
 //     per-block int64 partials and a finalize launch: no atomics, bitwise run to run
-// Rows are read as in krum.hip / clip.hip: four floats per lane, one 16-byte load where the row
-// start is 16-byte aligned, four scalar loads otherwise (CPT < 4: scalar loads); the last,
-// partial step reads only the row's remaining floats and stores only their results.
+// Rows are read CPT floats per lane: as in rowquad.hpp for CPT = 4 (ld_group below is this file's
+// own form of that load: through the shared one the kernels compile to other code), scalar loads
+// for CPT < 4; the last, partial step reads only the row's remaining floats and stores only
+// their results.
 #include "common.hpp"
+#include "rowquad.hpp"
 #include "sortnet.hpp"
 #include <algorithm>
 
@@ -35,7 +37,6 @@
 namespace {
 
 constexpr int kMaxRows = 64;
-constexpr int kQuad = 4;
 constexpr int kBlocksMax = 512;     // x 256 threads x 4 floats = 524288 elements per sweep of the grid
 constexpr uint32_t kNanKey = 0xFFFFFFFFu;
 
@@ -154,9 +155,9 @@ __global__ __launch_bounds__(256) void coord_trim_kernel(const float* __restrict
   unsigned long long vecmask = 0;
   if constexpr (CPT == kQuad) {
     for (int r = 0; r < n; ++r)
-      vecmask |= (unsigned long long)((((uintptr_t)row_start(buf, rstride, row_idx, r)) & 15) == 0) << r;
+      vecmask |= (unsigned long long)aligned16_dev(row_start(buf, rstride, row_idx, r)) << r;
   }
-  const bool base_vec = (((uintptr_t)base) & 15) == 0;
+  const bool base_vec = aligned16_dev(base);
   int count[N];
 #pragma unroll
   for (int r = 0; r < N; ++r) count[r] = 0;

@@ -15,7 +15,7 @@ from __future__ import annotations
 import copy
 import math
 import os
-from typing import Any, Dict, Iterable, List, Optional, Sequence
+from typing import Any, Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import yaml
 
@@ -177,36 +177,26 @@ class Params(dict):
         if self["aggregation_methods"] == AGGR_FOOLSGOLD and self["aggr_epoch_interval"] != 1:
             # reference image_train.py:24 'only works for aggr_epoch_interval=1'
             raise ValueError("foolsgold requires aggr_epoch_interval == 1")
-        if self.clip_norm is not None and self["aggregation_methods"] != AGGR_MEAN:
-            raise ValueError(f"clip_norm is an option of aggregation {AGGR_MEAN!r} "
-                             f"(got {self['aggregation_methods']!r})")
-        f, m = self.krum_f, self.krum_m
-        if f is None:
-            if m is not None:
-                raise ValueError("krum_m is set without krum_f")
-        else:
-            if self["aggregation_methods"] != AGGR_MEAN:
-                raise ValueError(f"krum_f is an option of aggregation {AGGR_MEAN!r} "
-                                 f"(got {self['aggregation_methods']!r})")
-            if self.clip_norm is not None:
-                raise ValueError("krum_f and clip_norm cannot be combined")
-            check_krum_sizes(int(self["no_models"]), f, m, "no_models")
-        t = self.trim_k
-        if t is not None:
-            if self["aggregation_methods"] != AGGR_MEAN:
-                raise ValueError(f"trim_k is an option of aggregation {AGGR_MEAN!r} "
-                                 f"(got {self['aggregation_methods']!r})")
-            if self.clip_norm is not None or f is not None:
-                raise ValueError("trim_k cannot be combined with clip_norm or krum_f")
-            check_trim_sizes(int(self["no_models"]), t, "no_models")
-        r = self.rlr_threshold
-        if r is not None:
-            if self["aggregation_methods"] != AGGR_MEAN:
-                raise ValueError(f"rlr_threshold is an option of aggregation {AGGR_MEAN!r} "
-                                 f"(got {self['aggregation_methods']!r})")
-            if self.clip_norm is not None or f is not None or t is not None:
-                raise ValueError("rlr_threshold cannot be combined with clip_norm, krum_f or trim_k")
-            check_rlr_sizes(int(self["no_models"]), r, "no_models")
+        # the options of "mean" (MEAN_OPTIONS): each on its own, and with "mean" only
+        earlier: List[str] = []
+        earlier_on = False
+        for opt in MEAN_OPTIONS:
+            on = getattr(self, opt.key) is not None
+            for k in opt.companions:
+                if getattr(self, k) is not None and not on:
+                    raise ValueError(f"{k} is set without {opt.key}")
+            if on:
+                if self["aggregation_methods"] != AGGR_MEAN:
+                    raise ValueError(f"{opt.key} is an option of aggregation {AGGR_MEAN!r} "
+                                     f"(got {self['aggregation_methods']!r})")
+                if earlier_on:
+                    others = (f"and {earlier[0]} cannot be combined" if len(earlier) == 1 else
+                              f"cannot be combined with {', '.join(earlier[:-1])} or {earlier[-1]}")
+                    raise ValueError(f"{opt.key} {others}")
+                if opt.sizes is not None:
+                    opt.sizes(self, int(self["no_models"]), "no_models")
+            earlier.append(opt.key)
+            earlier_on = earlier_on or on
 
     @property
     def type(self) -> str:
@@ -354,6 +344,32 @@ def check_rlr_sizes(n: int, theta: int, what: str = "n") -> int:
     if theta < 1 or theta > n:
         raise ValueError(f"rlr_threshold {theta} needs 1 <= theta <= {what} (got {n})")
     return theta
+
+
+class MeanOption(NamedTuple):
+    """One option of aggregation ``"mean"``.  ``Params.<key>`` is its checked value (None: off)."""
+    key: str
+    companions: Tuple[str, ...]     # keys that mean nothing without it
+    gathers: bool                   # the rule reads every client's final row on every rank
+    sizes: Optional[Callable[["Params", int, str], Any]]   # the rule's inequalities for n clients
+
+
+# in the order ``Server._aggregate`` looks for them; at most one is set
+MEAN_OPTIONS = (
+    MeanOption("clip_norm", (), False, None),
+    MeanOption("krum_f", ("krum_m",), True, lambda p, n, what: check_krum_sizes(n, p.krum_f, p.krum_m, what)),
+    MeanOption("trim_k", (), True, lambda p, n, what: check_trim_sizes(n, p.trim_k, what)),
+    MeanOption("rlr_threshold", (), False, lambda p, n, what: check_rlr_sizes(n, p.rlr_threshold, what)),
+)
+MEAN_OPTION_KEYS = tuple(k for opt in MEAN_OPTIONS for k in (opt.key,) + opt.companions)
+
+
+def mean_option(p: Params) -> Optional[MeanOption]:
+    """The option of aggregation ``"mean"`` that ``p`` sets (None: plain FedAvg)."""
+    for opt in MEAN_OPTIONS:
+        if getattr(p, opt.key) is not None:
+            return opt
+    return None
 
 
 def _same_client(a: Any, b: Any) -> bool:

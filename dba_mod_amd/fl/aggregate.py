@@ -1,13 +1,19 @@
 """Server-side aggregation over flat client buffers.
 
-Inputs are the round's client states ``finals [n, S]`` (or summed gradients for FoolsGold),
-already gathered onto every rank; each rank applies the identical update redundantly, so no
-broadcast is needed and every rank ends the round with a bit-identical global model.
+Each rule is ONE function, used by ``Server._aggregate`` and on a single rank alike.  Where the
+round's n client rows live is an argument: the rules whose sums decompose over clients (FedAvg,
+``clip_norm``, ``rlr_threshold``, distributed RFA) take this rank's rows ``finals [len(idx), S]`` and
+a :class:`Shard` (the positions ``idx`` of those rows among the n, a sum and a max over the ranks;
+default: every row here, identity reductions); the rules that read every row (``krum_f``,
+``trim_k``) take the server's gathered snapshot bank and the clients' slots ``row_idx`` and read
+the rows in place.  Every rank applies the identical update redundantly, so no broadcast is
+needed and every rank ends the round with a bit-identical global model.  A rule returns what the
+server records: the two ``weight_result.csv`` columns (and what its log line needs).
 
-* :func:`fedavg` / :func:`fedavg_apply` — reference ``helper.py:240-257``: ``w += (eta/no_models)
+* :func:`fedavg` — reference ``helper.py:240-257``: ``w += (eta/no_models)
   * sum_i delta_i`` (+ N(0, sigma) per element with ``diff_privacy``); unweighted; applied to
   the BN running stats too (D2).  The delta sum is an fp64 HIP reduction, per rank then
-  all-reduced (``Server._aggregate``).  The int64 ``num_batches_tracked`` counters are not part of the float
+  summed over the ranks.  The int64 ``num_batches_tracked`` counters are not part of the float
   bucket (D1: the reference's float→int64 add crashes on modern torch).
 * :func:`fedavg_clipped` / :func:`clip_factors` — norm-clipped FedAvg (config ``clip_norm``, not in
   the reference): each client's update is scaled to an L2 norm of at most C (fixed, or the round's
@@ -27,7 +33,7 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   pass over the strided final states (``ops.trimmed_delta_sum``: each coordinate sorted in
   registers, the kept ranks added in ascending order in fp64, so every bit is fixed by IEEE
   arithmetic) also counts, per client, the coordinates at which it was kept or cut.
-* :func:`fedavg_rlr` / :func:`rlr_finish` / :func:`rlr_theta` — robust learning rate (config
+* :func:`fedavg_rlr` / :func:`rlr_theta` — robust learning rate (config
   ``rlr_threshold``; Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference): per coordinate
   the signs of the clients' updates are summed and the averaged update is applied with a negative
   rate wherever the vote's |sum| is below theta; magnitudes play no part.  The fp64 delta sum and the
@@ -36,10 +42,9 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
   ``ops.rlr_apply`` (``add_noise_scaled``'s bits with ``+coef`` / ``-coef``).  Sums over clients
   decompose, so the clients stay on their owner ranks and every quantity is an integer or an fp64
   sum in client order.
-* :func:`geometric_median` / :func:`geometric_median_distributed` — RFA / Weiszfeld,
-  ``helper.py:295-373`` (the latter with the points resident on their owner ranks): one batched distance
-  kernel (all n clients in one pass) and one weighted-sum kernel per iteration; weights and
-  the stopping test stay on the device (one host read per aggregation).  Quirk D5 (``wv`` undefined if
+* :func:`geometric_median` — RFA / Weiszfeld, ``helper.py:295-373`` (on the gathered rows, or
+  with the points resident on their owner ranks): one batched distance kernel (all n clients in
+  one pass) and one weighted-sum kernel per iteration; weights and the stopping test stay on the device (one host read per aggregation).  Quirk D5 (``wv`` undefined if
   converged at iteration 0) resolves to the current weights.
 * The weighted sums of RFA and FoolsGold are REPRODUCIBLE: every product is quantised on its own
   onto a fixed two-limb int64 grid (:func:`fixed_exponent`, ``ops.weighted_sum_fixed``) and the
@@ -51,9 +56,10 @@ broadcast is needed and every rank ends the round with a bit-identical global mo
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
 import math
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -64,18 +70,46 @@ from .. import ops
 log = logging.getLogger("logger")
 
 
+@dataclasses.dataclass
+class Shard:
+    """Where a round's ``n`` client rows live: this rank holds the rows of the clients at positions
+    ``idx`` (in that order); ``reduce(t)`` sums a tensor over the ranks and ``reduce_max(v)`` takes
+    the max of a host float over them.  The default is the single-rank case: every row here,
+    identity reductions.  ``Server`` passes its own ``_reduce`` / ``_reduce_max``."""
+    n: int
+    idx: Optional[Sequence[int]] = None
+    reduce: Callable[[torch.Tensor], torch.Tensor] = lambda t: t
+    reduce_max: Callable[[float], float] = lambda v: v
+
+    def __post_init__(self) -> None:
+        self.idx = list(range(self.n) if self.idx is None else self.idx)
+        self._idx_t: Optional[torch.Tensor] = None
+
+    def index(self, device) -> torch.Tensor:
+        """``idx`` as an int64 tensor on ``device``."""
+        if self._idx_t is None or self._idx_t.device != torch.device(device):
+            self._idx_t = torch.tensor(self.idx, dtype=torch.int64, device=device)
+        return self._idx_t
+
+    def sum_rows(self, vals: Optional[torch.Tensor], tail: Tuple[int, ...], dtype, device) -> torch.Tensor:
+        """The [n, *tail] tensor of a per-client quantity from this rank's rows' ``vals``
+        [len(idx), *tail] (None on a rank without clients): zeros at the other ranks' clients,
+        summed over the ranks (each row owned by one rank, zero elsewhere: exact)."""
+        full = torch.zeros((self.n,) + tuple(tail), dtype=dtype, device=device)
+        if self.idx:
+            full[self.index(device)] = vals
+        return self.reduce(full)
+
+
 def fedavg(global_state: torch.Tensor, finals: torch.Tensor, eta: float, no_models: int,
-           dp: bool, sigma: float, seed: int, n_update: int) -> None:
-    """In-place FedAvg of ``finals`` [n, S]; ``n_update`` = leading entries aggregated (S or P)."""
-    fedavg_apply(global_state, ops.delta_sum(finals[:, :n_update], global_state[:n_update]), eta, no_models,
-                 dp, sigma, seed, n_update)
-
-
-def fedavg_apply(global_state: torch.Tensor, delta_sum: torch.Tensor, eta: float, no_models: int,
-                 dp: bool, sigma: float, seed: int, n_update: int) -> None:
-    """``w += (eta / no_models) * sum_i delta_i (+ noise)`` from the (all-reduced) fp64 sum of the
-    clients' deltas (``ops.delta_sum``: fused HIP kernel on GPU)."""
-    ops.add_noise_scaled(global_state[:n_update], delta_sum, eta / no_models, sigma, seed, dp)
+           dp: bool, sigma: float, seed: int, n_update: int, where: Optional[Shard] = None) -> None:
+    """In-place FedAvg of this rank's ``finals`` [len(idx), S]: ``w += (eta / no_models) * sum_i
+    delta_i (+ noise)``; ``n_update`` = leading entries aggregated (S or P).  Each rank sums its
+    own clients' deltas in fp64 (``ops.delta_sum``: fused HIP kernel on GPU), one reduction of
+    ``n_update`` values."""
+    where = where or Shard(finals.shape[0])
+    part = ops.delta_sum(finals[:, :n_update], global_state[:n_update])
+    ops.add_noise_scaled(global_state[:n_update], where.reduce(part), eta / no_models, sigma, seed, dp)
 
 
 FIXED_MAX_TERMS = 512
@@ -142,15 +176,21 @@ def clip_factors(sqnorms: torch.Tensor, clip) -> Tuple[torch.Tensor, float]:
     host, C).  A NaN norm (a NaN client update) gives a NaN factor, which carries the NaN into the
     aggregate."""
     norms = sqnorms.detach().double().cpu().sqrt()
-    n = norms.numel()
-    if isinstance(clip, str):
-        if clip != "median":
-            raise ValueError(f"clip {clip!r}: expected a bound or 'median'")
-        bound = float(torch.sort(norms).values[(n - 1) // 2]) if n else 0.0
-    else:
-        bound = float(clip)
+    bound = clip_bound(norms, clip)
     factors = torch.where(norms <= bound, torch.ones_like(norms), bound / norms)
     return factors, bound
+
+
+def clip_bound(norms: Sequence[float], clip) -> float:
+    """The bound C of a round with the update ``norms`` (fp64, on the host): ``clip`` itself, or
+    their lower median for ``"median"``."""
+    if not isinstance(clip, str):
+        return float(clip)
+    if clip != "median":
+        raise ValueError(f"clip {clip!r}: expected a bound or 'median'")
+    norms = torch.as_tensor(norms, dtype=torch.float64)
+    n = norms.numel()
+    return float(torch.sort(norms).values[(n - 1) // 2]) if n else 0.0
 
 
 def clipped_part(rows: torch.Tensor, base: torch.Tensor, scale: torch.Tensor, E: Optional[int]) -> torch.Tensor:
@@ -162,20 +202,27 @@ def clipped_part(rows: torch.Tensor, base: torch.Tensor, scale: torch.Tensor, E:
 
 
 def fedavg_clipped(global_state: torch.Tensor, finals: torch.Tensor, clip, eta: float, no_models: int,
-                   dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
-    """In-place norm-clipped FedAvg of ``finals`` [n, S] (single rank): ``w += (eta / no_models) *
-    sum_i s_i delta_i (+ noise)`` with the factors of :func:`clip_factors`.  The norm is taken over
-    the ``n_update`` leading entries, exactly the entries aggregated.  The clipped sum goes through
-    the fixed-point limbs (the bits ``Server._aggregate`` reaches from rank partials at any world
-    size); a non-finite update takes the fp64 sum and reaches the model.  Returns (factors, norms)."""
+                   dp: bool, sigma: float, seed: int, n_update: int, where: Optional[Shard] = None
+                   ) -> Tuple[List[float], List[float]]:
+    """In-place norm-clipped FedAvg of this rank's ``finals`` [len(idx), S]: ``w += (eta /
+    no_models) * sum_i s_i delta_i (+ noise)`` with the factors of :func:`clip_factors`.  The norm
+    is taken over the ``n_update`` leading entries, exactly the entries aggregated.  Every rank
+    takes the norms and max |delta| of its own clients in one fused pass; ONE reduction of the [n]
+    fp64 squared norms and ONE max of a host float; every rank then computes the same factors and
+    forms its partial clipped sum as fixed-point limbs; ONE reduction of the [2, n_update] int64
+    limbs (exact, so the global model's bits do not depend on the world size or on which rank
+    holds which client; fp64 partials if an update is not finite: the NaN reaches the model).
+    Returns (factors [n], norms [n])."""
+    where = where or Shard(finals.shape[0])
     rows, base = finals[:, :n_update], global_state[:n_update]
-    n = finals.shape[0]
-    sq, mx = ops.delta_stats(rows, base)
+    dev, idx = base.device, where.idx
+    sq_l, mx_l = ops.delta_stats(rows, base) if idx else (None, None)
+    sq = where.sum_rows(sq_l, (), torch.float64, dev)
     factors, _ = clip_factors(sq, clip)
-    E = fixed_exponent(max_abs(mx), n)
-    part = clipped_part(rows, base, factors.to(base.device), E) if n else wsum_zero(n_update, E, base.device)
-    total = part if E is None else fixed_decode(part, E)
-    ops.add_noise_scaled(global_state[:n_update], total, eta / no_models, sigma, seed, dp)
+    E = fixed_exponent(where.reduce_max(max_abs(mx_l)), where.n)
+    part = clipped_part(rows, base, factors[idx].to(dev), E) if idx else wsum_zero(n_update, E, dev)
+    total = where.reduce(part)
+    ops.add_noise_scaled(base, total if E is None else fixed_decode(total, E), eta / no_models, sigma, seed, dp)
     return [float(x) for x in factors], [float(x) for x in sq.double().cpu().sqrt()]
 
 
@@ -215,25 +262,24 @@ def krum_select(scores: torch.Tensor, m: int) -> List[int]:
 
 
 def fedavg_krum(global_state: torch.Tensor, finals: torch.Tensor, f: int, m: Optional[int], eta: float,
-                dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
-    """In-place Multi-Krum of ``finals`` [n, S] (single rank): the squared distances between the
-    clients' states over the ``n_update`` leading entries (exactly the entries aggregated;
-    ``ops.pairwise_sq_dists``: one fused HIP pass), the scores, the ``m`` (default n - f) best, then
-    ``w += (eta / m_sel) * sum_{i selected} (finals_i - w) (+ noise)`` with the plain FedAvg delta
-    sum over the selected rows in client order.  Returns (selected mask [n], scores [n])."""
-    n = finals.shape[0]
-    D = ops.pairwise_sq_dists(finals[:, :n_update])
+                dp: bool, sigma: float, seed: int, n_update: int, row_idx: Optional[Sequence[int]] = None
+                ) -> Tuple[List[float], List[float]]:
+    """In-place Multi-Krum of the n clients' final states: the rows ``row_idx`` of ``finals`` (the
+    server's gathered snapshot bank, read in place) or all of ``finals`` [n, S].  The squared
+    distances between the states over the ``n_update`` leading entries (exactly the entries
+    aggregated; ``ops.pairwise_sq_dists``: one fused HIP pass), the scores, the ``m`` (default n -
+    f) best, then ``w += (eta / m_sel) * sum_{i selected} (finals_i - w) (+ noise)`` with the plain
+    FedAvg delta sum over the selected rows (the only ones gathered) in client order.  Every rank
+    holds every row and computes the same bits redundantly: no reduction.  Returns (selected mask
+    [n], scores [n])."""
+    n = finals.shape[0] if row_idx is None else len(row_idx)
+    D = ops.pairwise_sq_dists(finals[:, :n_update], row_idx)
     scores = krum_scores(D, f)
     sel = krum_select(scores, n - f if m is None else m)
-    krum_apply(global_state, finals[sel], len(sel), eta, dp, sigma, seed, n_update)
-    return [1.0 if i in sel else 0.0 for i in range(n)], [float(x) for x in scores]
-
-
-def krum_apply(global_state: torch.Tensor, selected: torch.Tensor, m_sel: int, eta: float, dp: bool, sigma: float,
-               seed: int, n_update: int) -> None:
-    """``w += (eta / m_sel) * sum_i (selected_i - w) (+ noise)`` over the gathered selected rows."""
+    selected = finals[sel if row_idx is None else [row_idx[i] for i in sel]]
     total = ops.delta_sum(selected[:, :n_update], global_state[:n_update])
-    ops.add_noise_scaled(global_state[:n_update], total, eta / m_sel, sigma, seed, dp)
+    ops.add_noise_scaled(global_state[:n_update], total, eta / len(sel), sigma, seed, dp)
+    return [1.0 if i in sel else 0.0 for i in range(n)], [float(x) for x in scores]
 
 
 def trim_count(n: int, trim_k) -> int:
@@ -247,23 +293,19 @@ def trim_count(n: int, trim_k) -> int:
 
 
 def fedavg_trimmed(global_state: torch.Tensor, finals: torch.Tensor, k_or_median, eta: float, dp: bool,
-                   sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float]]:
-    """In-place coordinate-wise trimmed mean of ``finals`` [n, S] (single rank): per coordinate of
-    the ``n_update`` leading entries the k smallest and k largest client values are dropped
-    (``ops.trimmed_delta_sum``: one fused HIP pass, the sort in registers) and ``w += (eta / (n -
-    2 k)) * total (+ noise)``.  Returns (kept share [n], high share [n]): the fraction of the
+                   sigma: float, seed: int, n_update: int, row_idx: Optional[Sequence[int]] = None
+                   ) -> Tuple[List[float], List[float]]:
+    """In-place coordinate-wise trimmed mean of the n clients' final states: the rows ``row_idx``
+    of ``finals`` (the server's gathered snapshot bank, read in place) or all of ``finals`` [n, S].
+    Per coordinate of the ``n_update`` leading entries the k smallest and k largest client values
+    are dropped (``ops.trimmed_delta_sum``: one fused HIP pass, the sort in registers) and ``w +=
+    (eta / (n - 2 k)) * total (+ noise)``.  Every rank holds every row and computes the same bits
+    redundantly: no reduction.  (Sharding the coordinates over the ranks and all-gathering the
+    totals would move fewer bytes.)  Returns (kept share [n], high share [n]): the fraction of the
     aggregated coordinates at which each client's value was kept / cut as too high."""
-    n = finals.shape[0]
+    n = finals.shape[0] if row_idx is None else len(row_idx)
     k = trim_count(n, k_or_median)
-    total, kept, high = ops.trimmed_delta_sum(finals[:, :n_update], global_state[:n_update], k)
-    return trimmed_apply(global_state, total, kept, high, n, k, eta, dp, sigma, seed, n_update)
-
-
-def trimmed_apply(global_state: torch.Tensor, total: torch.Tensor, kept: torch.Tensor, high: torch.Tensor, n: int,
-                  k: int, eta: float, dp: bool, sigma: float, seed: int, n_update: int
-                  ) -> Tuple[List[float], List[float]]:
-    """``w += (eta / (n - 2 k)) * total (+ noise)`` from the fp64 trimmed sum; the counts as shares
-    of the ``n_update`` coordinates."""
+    total, kept, high = ops.trimmed_delta_sum(finals[:, :n_update], global_state[:n_update], k, row_idx)
     ops.add_noise_scaled(global_state[:n_update], total, eta / (n - 2 * k), sigma, seed, dp)
     den = float(max(1, n_update))
     return [float(v) / den for v in kept.tolist()], [float(v) / den for v in high.tolist()]
@@ -279,28 +321,34 @@ def rlr_theta(n: int, theta) -> int:
 
 
 def fedavg_rlr(global_state: torch.Tensor, finals: torch.Tensor, theta: int, eta: float, no_models: int,
-               dp: bool, sigma: float, seed: int, n_update: int) -> Tuple[List[float], List[float], int]:
-    """In-place robust-learning-rate FedAvg of ``finals`` [n, S] (single rank): per coordinate of
-    the ``n_update`` leading entries the clients' signs are summed (``ops.delta_sum_votes``: one
-    fused HIP pass that also gives plain FedAvg's fp64 delta sum) and ``w += (eta / no_models) *
-    total (+ noise)`` where ``|V| >= theta``, ``w -= ...`` where it is not (``ops.rlr_apply``).  Returns
-    (agree share [n], dissent share [n], flipped): the fraction of the aggregated coordinates that
-    were kept and at which each client's non-zero sign agreed with / opposed the vote
-    (``ops.vote_agreement``, against the old ``w``), and the number of flipped coordinates."""
-    n = finals.shape[0]
-    theta = rlr_theta(n, theta)
-    rows, base = finals[:, :n_update], global_state[:n_update]
-    total, votes = ops.delta_sum_votes(rows, base)
-    counts = ops.vote_agreement(rows, base, votes, theta)
-    return rlr_finish(global_state, total, votes, counts, theta, eta, no_models, dp, sigma, seed, n_update)
-
-
-def rlr_finish(global_state: torch.Tensor, total: torch.Tensor, votes: torch.Tensor, counts: torch.Tensor,
-               theta: int, eta: float, no_models: int, dp: bool, sigma: float, seed: int, n_update: int
+               dp: bool, sigma: float, seed: int, n_update: int, where: Optional[Shard] = None
                ) -> Tuple[List[float], List[float], int]:
-    """The robust-learning-rate update from the (all-reduced) fp64 delta sum, int32 votes and
-    [n, 2] int64 agreement counts; the counts as shares of the ``n_update`` coordinates."""
-    flipped = ops.rlr_apply(global_state[:n_update], total, votes, theta, eta / no_models, sigma, seed, dp)
+    """In-place robust-learning-rate FedAvg of this rank's ``finals`` [len(idx), S]: per coordinate
+    of the ``n_update`` leading entries the clients' signs are summed (``ops.delta_sum_votes``: one
+    fused HIP pass that also gives plain FedAvg's fp64 delta sum) and ``w += (eta / no_models) *
+    total (+ noise)`` where ``|V| >= theta``, ``w -= ...`` where it is not (``ops.rlr_apply``).  Sign
+    sums and delta sums decompose over clients: every rank takes those of its own clients (zeros on
+    a rank without clients); ONE reduction of the fp64 total (the one plain FedAvg does) and ONE of
+    the int32 votes (integer addition: exact); every rank then counts its own clients' agreement
+    with the reduced votes, against the old ``w`` (``ops.vote_agreement``); ONE reduction of the
+    [n, 2] int64 counts; every rank applies the signed update redundantly.  Returns (agree share
+    [n], dissent share [n], flipped): the fraction of the aggregated coordinates that were kept
+    and at which each client's non-zero sign agreed with / opposed the vote, and the number of
+    flipped coordinates."""
+    where = where or Shard(finals.shape[0])
+    theta = rlr_theta(where.n, theta)
+    rows, base = finals[:, :n_update], global_state[:n_update]
+    dev = base.device
+    if where.idx:
+        total, votes = ops.delta_sum_votes(rows, base)
+    else:
+        total = torch.zeros(n_update, dtype=torch.float64, device=dev)
+        votes = torch.zeros(n_update, dtype=torch.int32, device=dev)
+    total = where.reduce(total)
+    votes = where.reduce(votes)
+    agreement = ops.vote_agreement(rows, base, votes, theta) if where.idx else None
+    counts = where.sum_rows(agreement, (2,), torch.int64, dev)
+    flipped = ops.rlr_apply(base, total, votes, theta, eta / no_models, sigma, seed, dp)
     den = float(max(1, n_update))
     c = counts.cpu().tolist()
     return [float(a) / den for a, _ in c], [float(d) / den for _, d in c], int(flipped)
@@ -360,23 +408,36 @@ def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol:
 
 def geometric_median(global_state: torch.Tensor, finals: torch.Tensor, num_samples: Sequence[int],
                      eta: float, maxiter: int, dp: bool, sigma: float, seed: int, n_update: int,
-                     eps: float = 1e-5, ftol: float = 1e-6,
-                     max_update_norm: Optional[float] = None) -> Tuple[bool, List[float], List[float], int]:
-    """Weiszfeld geometric median of the client deltas; returns (updated, wv, alphas, oracle calls)."""
-    points = finals[:, :n_update] - global_state[None, :n_update]
-    a = torch.tensor(num_samples, dtype=torch.float64, device=points.device)
+                     eps: float = 1e-5, ftol: float = 1e-6, max_update_norm: Optional[float] = None,
+                     where: Optional[Shard] = None) -> Tuple[bool, List[float], List[float], int]:
+    """Weiszfeld geometric median of the client deltas (reference ``helper.py:320-352``) over this
+    rank's ``finals`` [len(idx), S]; returns (updated, wv, alphas, oracle calls).  Per iteration each
+    rank forms its partial weighted sum of its own points as fixed-point limbs (one reduction of
+    the [2, n_update] int64 limbs: exact, so the median's bits are the same at any world size) and
+    its points' distances to the median (one reduction of an n-vector with zeros for other ranks'
+    clients: exact); the fixed grid's exponent comes from the max |delta| over all clients (one max
+    of a host float).  ``where`` None: every row is here (a single rank, or the server's gather
+    mode) and nothing is reduced; with the points resident on their owner ranks the convergence
+    flag is polled every second iteration (each further one is two reductions)."""
+    poll = 0 if where is None else 2
+    where = where or Shard(finals.shape[0])
+    n, idx, dev = len(num_samples), where.idx, global_state.device
+    points = finals[:, :n_update] - global_state[None, :n_update] if idx else None
+    a = torch.tensor(num_samples, dtype=torch.float64, device=dev)
     alphas = a / a.sum()
-    E = fixed_exponent(max_abs(points), points.shape[0])
+    E = fixed_exponent(where.reduce_max(max_abs(points)), n)
 
     def avg(w: torch.Tensor) -> torch.Tensor:
-        # exact fixed-point sum of the products (each quantised on its own): the bits the
-        # distributed form reaches from its rank partials
-        return wsum_decode(wsum_part(points, w / w.sum(), E), E)
+        # exact fixed-point sum of the products (each quantised on its own)
+        wn = w / w.sum()
+        part = wsum_part(points, wn[where.index(dev)], E) if idx else wsum_zero(n_update, E, dev)
+        return wsum_decode(where.reduce(part), E)
 
     def dists(m: torch.Tensor) -> torch.Tensor:
-        return ops.sq_dists(points, m).double().clamp(min=0.0).sqrt()
+        sq = ops.sq_dists(points, m).double() if idx else None
+        return where.sum_rows(sq, (), torch.float64, dev).clamp(min=0.0).sqrt()
 
-    median, d, wv, iters = _weiszfeld(avg, dists, alphas, maxiter, eps, ftol)
+    median, d, wv, iters = _weiszfeld(avg, dists, alphas, maxiter, eps, ftol, poll)
     return _rfa_apply(global_state, median, d, wv, eta, dp, sigma, seed, n_update, max_update_norm, iters)
 
 
@@ -389,43 +450,6 @@ def _rfa_apply(global_state, median, d, wv, eta, dp, sigma, seed, n_update, max_
         log.info(f"\t\t\tUpdate norm = {upd_norm} is too large. Update rejected")
         updated = False
     return updated, [float(x) for x in wv], [float(x) for x in d.cpu().tolist()], 1 + iters
-
-
-def geometric_median_distributed(global_state: torch.Tensor, local_finals: torch.Tensor, local_idx: Sequence[int],
-                                 num_samples: Sequence[int], eta: float, maxiter: int, dp: bool, sigma: float,
-                                 seed: int, n_update: int, reduce, reduce_max=None, eps: float = 1e-5,
-                                 ftol: float = 1e-6, max_update_norm: Optional[float] = None
-                                 ) -> Tuple[bool, List[float], List[float], int]:
-    """Weiszfeld with the client deltas resident on their owner ranks (reference
-    ``helper.py:320-352``): per iteration each rank forms its partial weighted sum of its own
-    points as fixed-point limbs (``reduce`` = all-reduce of the [2, S] int64 limbs: exact, so the
-    median's bits equal :func:`geometric_median`'s at any world size) and its points' distances
-    to the median (all-reduce of an n-vector with zeros for other ranks' clients: exact).
-    ``reduce_max``: max-all-reduce of a host float (the fixed grid's exponent: the max |delta|
-    over all clients).  Same device-side iteration control and stopping rule."""
-    n = len(num_samples)
-    dev = global_state.device
-    idx = list(local_idx)
-    points = local_finals[:, :n_update] - global_state[None, :n_update] if idx else None
-    a = torch.tensor(num_samples, dtype=torch.float64, device=dev)
-    alphas = a / a.sum()
-    idx_t = torch.tensor(idx, dtype=torch.int64, device=dev) if idx else None
-    mx = max_abs(points)
-    E = fixed_exponent(reduce_max(mx) if reduce_max is not None else mx, n)
-
-    def avg(w: torch.Tensor) -> torch.Tensor:
-        wn = w / w.sum()
-        part = wsum_part(points, wn[idx_t], E) if idx else wsum_zero(n_update, E, dev)
-        return wsum_decode(reduce(part), E)
-
-    def dists(m: torch.Tensor) -> torch.Tensor:
-        full = torch.zeros(n, dtype=torch.float64, device=dev)
-        if idx:
-            full[idx_t] = ops.sq_dists(points, m).double()
-        return reduce(full).clamp(min=0.0).sqrt()
-
-    median, d, wv, iters = _weiszfeld(avg, dists, alphas, maxiter, eps, ftol, poll=2)
-    return _rfa_apply(global_state, median, d, wv, eta, dp, sigma, seed, n_update, max_update_norm, iters)
 
 
 class FoolsGold:

@@ -215,11 +215,10 @@ class Server:
         if rounds <= 0:
             return
         p = self.params
-        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr", "clip_norm", "krum_f", "krum_m",
-                                    "trim_k", "rlr_threshold")}
+        saved = {k: p[k] for k in ("is_poison", "eta", "aggregation_methods", "lr") + C.MEAN_OPTION_KEYS}
         # (plain FedAvg: the warm start stands in for a checkpoint trained without a defence)
-        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN, "clip_norm": None,
-                  "krum_f": None, "krum_m": None, "trim_k": None, "rlr_threshold": None})
+        p.update({"is_poison": False, "eta": float(eta), "aggregation_methods": C.AGGR_MEAN})
+        p.update(dict.fromkeys(C.MEAN_OPTION_KEYS))
         if lr is not None:
             p["lr"] = float(lr)
         try:
@@ -560,8 +559,9 @@ class Server:
                 done_early = early.done if early is not None else set()
                 shared.update(plan.jobs[j].model for j in range(len(plan.jobs))
                               if j not in done_early and plan.jobs[j].model != 0)
+            option = C.mean_option(self.params)
             if ((self.params["aggregation_methods"] == C.AGGR_GEO_MED and self._rfa_gather(len(plan.clients)))
-                    or self.params.krum_f is not None or self.params.trim_k is not None):
+                    or (option is not None and option.gathers)):
                 # (Multi-Krum scores every client against every other, the trimmed mean sorts every
                 # coordinate over all clients: every rank needs every final row)
                 shared.update(c.final_snap for c in plan.clients)
@@ -626,41 +626,57 @@ class Server:
 
     def _aggregate(self, plan: RoundPlan, bank: torch.Tensor, local: Dict[str, Any],
                    adversarial: List[Any]) -> None:
+        """Select the round's rule from the params, call it, log, record.  The rules are the
+        functions of :mod:`aggregate` (rank-aware through ``agg.Shard``: this rank's clients, its
+        ``_reduce`` / ``_reduce_max``); the rules that read every final row (``_gather`` has
+        broadcast them into every rank's bank) take the bank and the clients' slots."""
         p = self.params
         method = p["aggregation_methods"]
         n_upd = self.spec.S if p["aggregate_bn_buffers"] else self.spec.P
         names = [c.name for c in plan.clients]
+        n = len(names)
+        slots = [c.final_snap for c in plan.clients]
+        g, finals = self.global_state, local["finals"]
+        where = agg.Shard(n, local["idx"], self._reduce, self._reduce_max)
+        eta, no_models = float(p["eta"]), int(p["no_models"])
         dp_seed = (int(p["seed"]) * 7919 + plan.epoch) & 0x7FFFFFFF
-        if method == C.AGGR_MEAN and p.clip_norm is not None:
-            self._aggregate_clipped(plan, local, names, adversarial, p.clip_norm, n_upd, dp_seed)
-        elif method == C.AGGR_MEAN and p.krum_f is not None:
-            self._aggregate_krum(plan, bank, names, adversarial, p.krum_f, p.krum_m, n_upd, dp_seed)
-        elif method == C.AGGR_MEAN and p.trim_k is not None:
-            self._aggregate_trimmed(plan, bank, names, adversarial, p.trim_k, n_upd, dp_seed)
-        elif method == C.AGGR_MEAN and p.rlr_threshold is not None:
-            self._aggregate_rlr(plan, local, names, adversarial, p.rlr_threshold, n_upd, dp_seed)
+        tail = (bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
+        option = C.mean_option(p) if method == C.AGGR_MEAN else None
+        key = option.key if option is not None else None
+        # the rule's inequalities against the round's actual client count: Krum's m, the trim count k, theta
+        size = option.sizes(p, n, "the round's clients") if option is not None and option.sizes else None
+        cols: Optional[Tuple[List[float], List[float]]] = None      # the two weight_result.csv columns
+
+        def starred(shares: List[float]) -> str:
+            return ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, shares))
+
+        if key == "clip_norm":
+            cols = agg.fedavg_clipped(g, finals, p.clip_norm, eta, no_models, *tail, where)
+            bound = agg.clip_bound(cols[1], p.clip_norm)
+            log.info(f"[clip agg] C: {bound}  clipped: {sum(v > bound for v in cols[1])}/{n}  factors: {cols[0]}")
+        elif key == "krum_f":
+            cols = agg.fedavg_krum(g, bank, p.krum_f, size, eta, *tail, row_idx=slots)
+            chosen = [nm for nm, on in zip(names, cols[0]) if on]
+            log.info(f"[krum agg] f: {p.krum_f}  m: {size}  selected: {chosen}  "
+                     f"adversaries selected: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}")
+        elif key == "trim_k":
+            cols = agg.fedavg_trimmed(g, bank, p.trim_k, eta, *tail, row_idx=slots)
+            log.info(f"[trim agg] k: {size}  n: {n}  kept share (* adversary): {starred(cols[0])}")
+        elif key == "rlr_threshold":
+            *cols, flipped = agg.fedavg_rlr(g, finals, p.rlr_threshold, eta, no_models, *tail, where)
+            log.info(f"[rlr agg] theta: {size}  n: {n}  flipped: {flipped}/{n_upd} ({flipped / max(1, n_upd):.4f})  "
+                     f"agree share (* adversary): {starred(cols[0])}")
         elif method == C.AGGR_MEAN:
-            # each rank sums its own clients' deltas (fp64), one all-reduce of S values
-            part = ops.delta_sum(local["finals"][:, :n_upd], self.global_state[:n_upd])
-            agg.fedavg_apply(self.global_state, self._reduce(part), float(p["eta"]), int(p["no_models"]),
-                             bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
+            agg.fedavg(g, finals, eta, no_models, *tail, where)
         elif method == C.AGGR_GEO_MED:
             ns = [c.num_samples for c in plan.clients]
             self._log_poison_ratio("rfa", names, ns)
             mun = p["max_update_norm"]
-            kw = dict(max_update_norm=float(mun) if mun is not None else None)
-            if self._rfa_gather(len(plan.clients)):
-                finals = bank[[c.final_snap for c in plan.clients]]
-                updated, wv, alphas, calls = agg.geometric_median(
-                    self.global_state, finals, ns, float(p["eta"]), int(p["geom_median_maxiter"]),
-                    bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd, **kw)
-            else:
-                updated, wv, alphas, calls = agg.geometric_median_distributed(
-                    self.global_state, local["finals"], local["idx"], ns, float(p["eta"]),
-                    int(p["geom_median_maxiter"]), bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd,
-                    reduce=self._reduce, reduce_max=self._reduce_max, **kw)
-            self.csv.add_weight_result(names, wv, alphas)
-            self._plot_weights(names, wv, alphas, adversarial, plan.epoch)
+            # every final row is in the bank (gather mode: nothing to reduce), or the points stay on their owners
+            gathered = self._rfa_gather(n)
+            _, *cols, _ = agg.geometric_median(
+                g, bank[slots] if gathered else finals, ns, eta, int(p["geom_median_maxiter"]), *tail,
+                max_update_norm=float(mun) if mun is not None else None, where=None if gathered else where)
         elif method == C.AGGR_FOOLSGOLD:
             ns = [c.num_samples for c in plan.clients]
             self._log_poison_ratio("foolsgold", names, ns)
@@ -688,125 +704,10 @@ class Server:
             agg.foolsgold_server_step(self.global_state, agg_grad, self.spec.P, float(p["eta"]),
                                       float(p["lr"]), float(p["decay"]))
             print("model aggregation took {}s".format(time.time() - t0))
-            self.csv.add_weight_result(names, wv.tolist(), alpha.tolist())
-            self._plot_weights(names, wv.tolist(), alpha.tolist(), adversarial, plan.epoch)
-
-    def _aggregate_clipped(self, plan: RoundPlan, local: Dict[str, Any], names: List[Any], adversarial: List[Any],
-                           clip: Any, n_upd: int, dp_seed: int) -> None:
-        """Norm-clipped FedAvg (``clip_norm``) on rank-resident clients: every rank takes the norms
-        and max |delta| of its own clients in one fused pass; ONE all-reduce of the [n] fp64
-        squared norms (each row owned by one rank, zero elsewhere: exact) and ONE max-all-reduce
-        of a host float; every rank then computes the same factors and forms its partial clipped
-        sum as fixed-point limbs; ONE all-reduce of the [2, n_upd] int64 limbs (exact, so the
-        global model's bits do not depend on the world size or on which rank holds which client;
-        fp64 partials if an update is not finite: the NaN reaches the model and nan_check aborts)."""
-        p = self.params
-        n = len(plan.clients)
-        idx = local["idx"]
-        rows, base = local["finals"][:, :n_upd], self.global_state[:n_upd]
-        sq = torch.zeros(n, dtype=torch.float64, device=self.device)
-        mx = 0.0
-        if idx:
-            idx_t = torch.tensor(idx, dtype=torch.int64, device=self.device)
-            sq_l, mx_l = ops.delta_stats(rows, base)
-            sq[idx_t] = sq_l
-            mx = agg.max_abs(mx_l)
-        sq = self._reduce(sq)
-        factors, bound = agg.clip_factors(sq, clip)
-        E = agg.fixed_exponent(self._reduce_max(mx), n)
-        if idx:
-            part = agg.clipped_part(rows, base, factors[idx].to(self.device), E)
-        else:
-            part = agg.wsum_zero(n_upd, E, self.device)
-        total = self._reduce(part)
-        ops.add_noise_scaled(base, total if E is None else agg.fixed_decode(total, E),
-                             float(p["eta"]) / int(p["no_models"]), float(p["sigma"]), dp_seed,
-                             bool(p["diff_privacy"]))
-        norms = sq.double().cpu().sqrt()
-        fl, nl = [float(x) for x in factors], [float(x) for x in norms]
-        log.info(f"[clip agg] C: {bound}  clipped: {int((norms > bound).sum())}/{n}  factors: {fl}")
-        self.csv.add_weight_result(names, fl, nl)
-        self._plot_weights(names, fl, nl, adversarial, plan.epoch)
-
-    def _aggregate_krum(self, plan: RoundPlan, bank: torch.Tensor, names: List[Any], adversarial: List[Any],
-                        f: int, m: Optional[int], n_upd: int, dp_seed: int) -> None:
-        """Multi-Krum (``krum_f``) on the gathered final states: ``_gather`` has broadcast every
-        client's final row into every rank's bank, so every rank computes the [n, n] squared
-        distances from the bank rows in place (one fused pass, the rows picked by their slots),
-        scores, selects and applies the selected clients' FedAvg redundantly.  No collective
-        follows the gather: the same rows in the same order through the same kernel give every
-        rank, at every world size, the same bits."""
-        p = self.params
-        n = len(plan.clients)
-        m = C.check_krum_sizes(n, f, m, "the round's clients")
-        slots = [c.final_snap for c in plan.clients]
-        D = ops.pairwise_sq_dists(bank[:, :n_upd], slots)
-        scores = agg.krum_scores(D, f)
-        sel = agg.krum_select(scores, m)
-        agg.krum_apply(self.global_state, bank[[slots[i] for i in sel]], len(sel), float(p["eta"]),
-                       bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
-        mask = [1.0 if i in sel else 0.0 for i in range(n)]
-        sc = [float(x) for x in scores]
-        chosen = [names[i] for i in sel]
-        log.info(f"[krum agg] f: {f}  m: {m}  selected: {chosen}  "
-                 f"adversaries selected: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}")
-        self.csv.add_weight_result(names, mask, sc)
-        self._plot_weights(names, mask, sc, adversarial, plan.epoch)
-
-    def _aggregate_trimmed(self, plan: RoundPlan, bank: torch.Tensor, names: List[Any], adversarial: List[Any],
-                           trim_k: Any, n_upd: int, dp_seed: int) -> None:
-        """Coordinate-wise trimmed mean / median (``trim_k``) on the gathered final states:
-        ``_gather`` has broadcast every client's final row into every rank's bank, so every rank
-        runs the same fused pass over the bank rows in place (picked by their slots) and applies the
-        trimmed sum redundantly.  No collective follows the gather: the same rows in the same order
-        through the same kernel give every rank, at every world size, the same bits.  (Sharding the
-        coordinates over the ranks and all-gathering the totals would move fewer bytes.)"""
-        p = self.params
-        n = len(plan.clients)
-        k = agg.trim_count(n, trim_k)
-        slots = [c.final_snap for c in plan.clients]
-        total, kept, high = ops.trimmed_delta_sum(bank[:, :n_upd], self.global_state[:n_upd], k, slots)
-        ks, hs = agg.trimmed_apply(self.global_state, total, kept, high, n, k, float(p["eta"]),
-                                   bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
-        shares = ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, ks))
-        log.info(f"[trim agg] k: {k}  n: {n}  kept share (* adversary): {shares}")
-        self.csv.add_weight_result(names, ks, hs)
-        self._plot_weights(names, ks, hs, adversarial, plan.epoch)
-
-    def _aggregate_rlr(self, plan: RoundPlan, local: Dict[str, Any], names: List[Any], adversarial: List[Any],
-                       rlr_threshold: int, n_upd: int, dp_seed: int) -> None:
-        """Robust learning rate (``rlr_threshold``) on rank-resident clients: sign sums and delta
-        sums decompose over clients, so every rank takes the fp64 delta sum and the int32 votes of
-        its own clients in one fused pass (zeros on a rank without clients); ONE all-reduce of the
-        fp64 total (the one plain FedAvg does) and ONE of the int32 votes (integer addition: exact);
-        every rank then counts its own clients' agreement with the reduced votes, against the old
-        global state; ONE all-reduce of the [n, 2] int64 counts (each row owned by one rank, zero
-        elsewhere); every rank applies the signed update redundantly.  No final state is broadcast."""
-        p = self.params
-        n = len(plan.clients)
-        theta = agg.rlr_theta(n, rlr_threshold)
-        idx = local["idx"]
-        rows, base = local["finals"][:, :n_upd], self.global_state[:n_upd]
-        if idx:
-            total, votes = ops.delta_sum_votes(rows, base)
-        else:
-            total = torch.zeros(n_upd, dtype=torch.float64, device=self.device)
-            votes = torch.zeros(n_upd, dtype=torch.int32, device=self.device)
-        total = self._reduce(total)
-        votes = self._reduce(votes)
-        counts = torch.zeros(n, 2, dtype=torch.int64, device=self.device)
-        if idx:
-            counts[torch.tensor(idx, dtype=torch.int64, device=self.device)] = ops.vote_agreement(rows, base, votes,
-                                                                                                  theta)
-        counts = self._reduce(counts)
-        ag, ds, flipped = agg.rlr_finish(self.global_state, total, votes, counts, theta, float(p["eta"]),
-                                         int(p["no_models"]), bool(p["diff_privacy"]), float(p["sigma"]), dp_seed,
-                                         n_upd)
-        shares = ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, ag))
-        log.info(f"[rlr agg] theta: {theta}  n: {n}  flipped: {flipped}/{n_upd} ({flipped / max(1, n_upd):.4f})  "
-                 f"agree share (* adversary): {shares}")
-        self.csv.add_weight_result(names, ag, ds)
-        self._plot_weights(names, ag, ds, adversarial, plan.epoch)
+            cols = (wv.tolist(), alpha.tolist())
+        if cols is not None:
+            self.csv.add_weight_result(names, *cols)
+            self._plot_weights(names, *cols, adversarial, plan.epoch)
 
     def _log_poison_ratio(self, tag: str, names: List[Any], ns: List[int]) -> None:
         p = self.params

@@ -1337,6 +1337,23 @@ def _delta_rows(rows, base):
     return rows, (rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), base.contiguous()
 
 
+def _picked_rows(op, buf, row_idx):
+    """(buf, row stride, row numbers as an int32 device tensor or None, n) of the kernels that read
+    n rows of the fp32 bank ``buf`` [R, L] where they lie: the rows ``row_idx`` (repeats allowed;
+    the kernels read ``row * stride`` unchecked, so every one is checked here) or all R."""
+    assert buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
+    if buf.shape[1] > 1 and buf.stride(1) != 1:
+        buf = buf.contiguous()
+    R, L = buf.shape
+    idx = None
+    if row_idx is not None:
+        rows = [int(r) for r in (row_idx.tolist() if isinstance(row_idx, Tensor) else row_idx)]
+        if not all(0 <= r < R for r in rows):
+            raise ValueError(f"{op}: row_idx {rows} outside the {R} rows of buf")
+        idx = torch.tensor(rows, dtype=torch.int32, device=buf.device)
+    return buf, (buf.stride(0) if R > 1 else L), idx, (R if idx is None else idx.numel())
+
+
 def _clip_scale(scale, n, device):
     """The [n] fp32 clip factors on the rows' device."""
     assert scale.numel() == n
@@ -1397,22 +1414,12 @@ def pairwise_sq_dists(buf, row_idx=None):
     accumulated once in fp64 and mirrored; no atomics, bitwise run to run, and a pair's bits do
     not depend on the rows' alignment or on the other rows of the call.  More than 64 rows take
     the reference composition on the device."""
-    assert buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
-    if buf.shape[1] > 1 and buf.stride(1) != 1:
-        buf = buf.contiguous()
-    R, L = buf.shape
-    idx = None
-    if row_idx is not None:
-        rows = [int(r) for r in (row_idx.tolist() if isinstance(row_idx, Tensor) else row_idx)]
-        if not all(0 <= r < R for r in rows):       # (the kernel reads rows[r] * stride unchecked)
-            raise ValueError(f"pairwise_sq_dists: row_idx {rows} outside the {R} rows of buf")
-        idx = torch.tensor(rows, dtype=torch.int32, device=buf.device)
-    n = R if idx is None else idx.numel()
+    buf, rs, idx, n = _picked_rows("pairwise_sq_dists", buf, row_idx)
+    L = buf.shape[1]
     if n > PAIRWISE_MAX_ROWS:
         return _ref.pairwise_sq_dists(buf, row_idx)
     if n < 2 or L == 0:
         return torch.zeros(n, n, dtype=torch.float64, device=buf.device)
-    rs = buf.stride(0) if R > 1 else L
     out = torch.empty(n, n, dtype=torch.float64, device=buf.device)
     nb = int(_L.dba_pairwise_sqdist_blocks(L))
     part = torch.empty(n * (n - 1) // 2 * nb, dtype=torch.float64, device=buf.device)
@@ -1429,19 +1436,10 @@ def trimmed_delta_sum(buf, base, k, row_idx=None):
     numbers into ``buf``, repeats allowed), each coordinate sorted in registers, ranks k .. n - 1 - k
     added in ascending order in fp64; no atomics, bitwise run to run.  More than 64 rows (or 2^31
     coordinates) take the reference composition on the device."""
-    assert buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
+    buf, rs, idx, n = _picked_rows("trimmed_delta_sum", buf, row_idx)
+    L = buf.shape[1]
     assert base.dtype == torch.float32 and base.device == buf.device
-    if buf.shape[1] > 1 and buf.stride(1) != 1:
-        buf = buf.contiguous()
-    R, L = buf.shape
     assert base.numel() == L, (tuple(buf.shape), base.numel())
-    idx = None
-    if row_idx is not None:
-        rows = [int(r) for r in (row_idx.tolist() if isinstance(row_idx, Tensor) else row_idx)]
-        if not all(0 <= r < R for r in rows):       # (the kernel reads rows[r] * stride unchecked)
-            raise ValueError(f"trimmed_delta_sum: row_idx {rows} outside the {R} rows of buf")
-        idx = torch.tensor(rows, dtype=torch.int32, device=buf.device)
-    n = R if idx is None else idx.numel()
     k = _ref.check_trim(n, k)
     if n > TRIM_MAX_ROWS or L >= 1 << 31:
         return _ref.trimmed_delta_sum(buf, base, k, row_idx)
@@ -1449,7 +1447,6 @@ def trimmed_delta_sum(buf, base, k, row_idx=None):
         return (torch.zeros(L, dtype=torch.float64, device=buf.device),
                 torch.zeros(n, dtype=torch.int64, device=buf.device),
                 torch.zeros(n, dtype=torch.int64, device=buf.device))
-    rs = buf.stride(0) if R > 1 else L
     base = base.contiguous()
     total = torch.empty(L, dtype=torch.float64, device=buf.device)
     counts = torch.empty(n, 2, dtype=torch.int64, device=buf.device)

@@ -608,6 +608,16 @@ def clipped_delta_sum(rows: Tensor, base: Tensor, scale: Tensor) -> Tensor:
 PAIRWISE_CHUNK = 1 << 18
 
 
+def _picked_rows(buf: Tensor, row_idx) -> Tuple[Optional[Tensor], int]:
+    """(row numbers as an int64 tensor or None, n) of the ops over n rows of ``buf`` [R, L]: the rows
+    ``row_idx`` (repeats allowed) or all R."""
+    assert buf.dim() == 2
+    if row_idx is None:
+        return None, buf.shape[0]
+    idx = torch.as_tensor(row_idx, dtype=torch.int64, device=buf.device).reshape(-1)
+    return idx, idx.numel()
+
+
 def pairwise_sq_dists(buf: Tensor, row_idx=None) -> Tensor:
     """fp64 [n, n] squared L2 distances between the rows of ``buf`` [R, L] fp32 (Multi-Krum;
     krum.hip pairwise_sqdist_kernel is the GPU form): rows ``row_idx`` (n row numbers, repeats
@@ -616,11 +626,7 @@ def pairwise_sq_dists(buf: Tensor, row_idx=None) -> Tensor:
     nearly equal client states).  Chunked over L, so no [n, n, L] temporary; each unordered pair
     is summed once and mirrored: symmetric, zero diagonal.  A NaN / Inf element makes its row's
     off-diagonal distances non-finite and leaves the others alone."""
-    assert buf.dim() == 2
-    idx = None
-    if row_idx is not None:
-        idx = torch.as_tensor(row_idx, dtype=torch.int64, device=buf.device).reshape(-1)
-    n = buf.shape[0] if idx is None else idx.numel()
+    idx, n = _picked_rows(buf, row_idx)
     L = buf.shape[1]
     D = torch.zeros(n, n, dtype=torch.float64, device=buf.device)
     if n < 2:
@@ -655,11 +661,7 @@ def trimmed_delta_sum(buf: Tensor, base: Tensor, k: int, row_idx=None) -> Tuple[
     if ``v > hi`` or v is NaN and hi is not, kept otherwise; clients tied with a threshold are all
     kept.  Returns (total fp64 [L], kept int64 [n], high int64 [n]): the coordinates each client
     was kept / cut as high at (low is L - kept - high).  Chunked over L: no [n, L] fp64."""
-    assert buf.dim() == 2
-    idx = None
-    if row_idx is not None:
-        idx = torch.as_tensor(row_idx, dtype=torch.int64, device=buf.device).reshape(-1)
-    n = buf.shape[0] if idx is None else idx.numel()
+    idx, n = _picked_rows(buf, row_idx)
     L = buf.shape[1]
     k = check_trim(n, k)
     total = torch.zeros(L, dtype=torch.float64, device=buf.device)
