@@ -15,11 +15,12 @@
 // Sums over clients decompose, so each rank runs the first two passes on its own rows and the
 // fp64 totals, int32 votes and int64 counts are all-reduced (fl/aggregate.py fedavg_rlr).
 // No atomics: the counts go through lanes in a fixed butterfly, the four waves in order, per-block
-// int64 partials and a finalize launch, so they are bitwise run to run; every other output
+// int64 partials and a finalize launch (countfin.hpp), so they are bitwise run to run; every other output
 // depends on its own coordinate alone, never on the launch grid.
 // Rows are read four floats per lane (rowquad.hpp); outputs take 16-byte stores where their own
 // start allows.
 #include "common.hpp"
+#include "countfin.hpp"
 #include "noise.hpp"
 #include "rowquad.hpp"
 #include <algorithm>
@@ -30,7 +31,6 @@ constexpr int kBlocksMax = 4096;   // sum + votes, apply: x 256 threads x 4 coor
 constexpr int kRowBatch = 4;       // rows whose loads are in flight together in the sum + votes pass
 constexpr int kAgreeBatch = 4;     // quads in flight per lane in the agreement pass
 constexpr int kAgreeBlocksMax = 1024;   // x 256 threads x kAgreeBatch x 4 coordinates = the same sweep
-constexpr int kFinalBatch = 4;     // partials in flight per thread in the finalize launch
 constexpr int kMaxGridY = 65535;
 
 // +1 / -1 / 0: fp32 comparisons (NaN on either side and -0 against +0 give 0)
@@ -210,27 +210,6 @@ __global__ __launch_bounds__(256) void vote_agreement_kernel(const float* __rest
     part[((long long)i * 2 + 0) * gridDim.x + blockIdx.x] = a;
     part[((long long)i * 2 + 1) * gridDim.x + blockIdx.x] = d;
   }
-}
-
-// one block per output slot: thread t takes the partials of blocks t, t + 256, ... (kFinalBatch
-// loads in flight: a chain of dependent L2 round trips over thousands of partials would take
-// longer than the pass over the rows), then the block combines in the fixed order of block_sum
-__global__ __launch_bounds__(256) void count_finalize(const long long* __restrict__ part, int nblk,
-                                                     long long* __restrict__ counts) {
-  __shared__ long long red[4];
-  const long long* p = part + (long long)blockIdx.x * nblk;
-  long long s = 0;
-  int b = threadIdx.x;
-  for (; b + (kFinalBatch - 1) * 256 < nblk; b += kFinalBatch * 256) {
-    long long v[kFinalBatch];
-#pragma unroll
-    for (int u = 0; u < kFinalBatch; ++u) v[u] = p[b + u * 256];
-#pragma unroll
-    for (int u = 0; u < kFinalBatch; ++u) s += v[u];
-  }
-  for (; b < nblk; b += 256) s += p[b];
-  s = block_sum<long long>(s, red);
-  if (threadIdx.x == 0) counts[blockIdx.x] = s;
 }
 
 }  // namespace

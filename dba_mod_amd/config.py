@@ -145,6 +145,18 @@ _DEFAULTS: Dict[str, Any] = {
     # update with a negative rate where the vote's |sum| is below theta.  None = off; an integer
     # theta with 1 <= theta <= no_models
     "rlr_threshold": None,
+    # SparseFed (aggregation "mean" only; Panda et al., AISTATS 2022): the round's aggregate is added
+    # into a server-side error-feedback residual and only the k largest-magnitude coordinates of the
+    # residual reach the model (and leave the residual); the rest wait there for later rounds.
+    # sparse_topk: None = off; a float fraction with 0 < frac <= 1, k = max(1, floor(frac * entries
+    # aggregated)) (an integer is an error: YAML 1 must not mean one coordinate).  Not with
+    # diff_privacy: noise on every coordinate undoes the sparsity, noise on the kept ones only
+    # publishes the support
+    "sparse_topk": None,
+    # sparse_clip (with sparse_topk only): each client's update is clipped before it enters the
+    # aggregate, with clip_norm's grammar: None = off; a finite number > 0 = C; "median" = the lower
+    # median of the round's client update norms
+    "sparse_clip": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -197,6 +209,9 @@ class Params(dict):
                     opt.sizes(self, int(self["no_models"]), "no_models")
             earlier.append(opt.key)
             earlier_on = earlier_on or on
+        if self.sparse_topk is not None and self["diff_privacy"]:
+            raise ValueError("sparse_topk cannot be combined with diff_privacy (noise on the dropped "
+                             "coordinates undoes the sparsity, noise on the kept ones publishes the support)")
 
     @property
     def type(self) -> str:
@@ -226,6 +241,16 @@ class Params(dict):
     def rlr_threshold(self) -> Optional[int]:
         """The checked ``rlr_threshold``: None (off) or theta >= 1."""
         return check_rlr_threshold(self.get("rlr_threshold"))
+
+    @property
+    def sparse_topk(self) -> Optional[float]:
+        """The checked ``sparse_topk``: None (SparseFed off) or the kept fraction in (0, 1]."""
+        return check_sparse_topk(self.get("sparse_topk"))
+
+    @property
+    def sparse_clip(self) -> Any:
+        """The checked ``sparse_clip``: None (off), the bound C as a float, or ``"median"``."""
+        return check_clip_norm(self.get("sparse_clip"), "sparse_clip")
 
     @property
     def adversary_list(self) -> List[Any]:
@@ -278,13 +303,14 @@ class Params(dict):
 CLIP_MEDIAN = "median"
 
 
-def check_clip_norm(v: Any) -> Any:
-    """None, a finite bound > 0 (returned as float) or ``"median"``; anything else is an error."""
+def check_clip_norm(v: Any, key: str = "clip_norm") -> Any:
+    """None, a finite bound > 0 (returned as float) or ``"median"``; anything else is an error
+    (``key``: the config key in the message; ``sparse_clip`` has the same grammar)."""
     if v is None or (isinstance(v, str) and v == CLIP_MEDIAN):
         return v
     if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
         return float(v)
-    raise ValueError(f"clip_norm {v!r}: expected None, a finite number > 0 or {CLIP_MEDIAN!r}")
+    raise ValueError(f"{key} {v!r}: expected None, a finite number > 0 or {CLIP_MEDIAN!r}")
 
 
 def check_krum_int(key: str, v: Any, lo: int) -> Optional[int]:
@@ -346,6 +372,16 @@ def check_rlr_sizes(n: int, theta: int, what: str = "n") -> int:
     return theta
 
 
+def check_sparse_topk(v: Any) -> Optional[float]:
+    """None or a float fraction with 0 < frac <= 1 (a bool, an int, a string or a list is an error:
+    an int is rejected so that 1 cannot be read as one coordinate)."""
+    if v is None:
+        return None
+    if isinstance(v, float) and 0.0 < v <= 1.0:
+        return v
+    raise ValueError(f"sparse_topk {v!r}: expected None or a float fraction with 0 < frac <= 1")
+
+
 class MeanOption(NamedTuple):
     """One option of aggregation ``"mean"``.  ``Params.<key>`` is its checked value (None: off)."""
     key: str
@@ -360,6 +396,7 @@ MEAN_OPTIONS = (
     MeanOption("krum_f", ("krum_m",), True, lambda p, n, what: check_krum_sizes(n, p.krum_f, p.krum_m, what)),
     MeanOption("trim_k", (), True, lambda p, n, what: check_trim_sizes(n, p.trim_k, what)),
     MeanOption("rlr_threshold", (), False, lambda p, n, what: check_rlr_sizes(n, p.rlr_threshold, what)),
+    MeanOption("sparse_topk", ("sparse_clip",), False, None),
 )
 MEAN_OPTION_KEYS = tuple(k for opt in MEAN_OPTIONS for k in (opt.key,) + opt.companions)
 

@@ -42,6 +42,14 @@ server records: the two ``weight_result.csv`` columns (and what its log line nee
   ``ops.rlr_apply`` (``add_noise_scaled``'s bits with ``+coef`` / ``-coef``).  Sums over clients
   decompose, so the clients stay on their owner ranks and every quantity is an integer or an fp64
   sum in client order.
+* :func:`fedavg_sparse` / :func:`sparse_count` — SparseFed (config ``sparse_topk``,
+  ``sparse_clip``; Panda et al., AISTATS 2022; not in the reference): the (optionally clipped)
+  total is added into a server-side fp64 error-feedback residual and only the k largest-magnitude
+  coordinates of the residual are applied and cleared; the rest wait in the residual.  The k-th
+  largest magnitude is an exact radix select on the device (``ops.topk_threshold``: integer
+  histograms, no host read inside) and the sparse update one pass (``ops.topk_apply``:
+  ``add_noise_scaled``'s bits at the kept coordinates, nothing written elsewhere).  The residual is
+  the one piece of server state besides FoolsGold's: every rank holds it, checkpoints carry it.
 * :func:`geometric_median` — RFA / Weiszfeld, ``helper.py:295-373`` (on the gathered rows, or
   with the points resident on their owner ranks): one batched distance kernel (all n clients in
   one pass) and one weighted-sum kernel per iteration; weights and the stopping test stay on the device (one host read per aggregation).  Quirk D5 (``wv`` undefined if
@@ -108,8 +116,14 @@ def fedavg(global_state: torch.Tensor, finals: torch.Tensor, eta: float, no_mode
     own clients' deltas in fp64 (``ops.delta_sum``: fused HIP kernel on GPU), one reduction of
     ``n_update`` values."""
     where = where or Shard(finals.shape[0])
-    part = ops.delta_sum(finals[:, :n_update], global_state[:n_update])
-    ops.add_noise_scaled(global_state[:n_update], where.reduce(part), eta / no_models, sigma, seed, dp)
+    total = delta_total(finals[:, :n_update], global_state[:n_update], where)
+    ops.add_noise_scaled(global_state[:n_update], total, eta / no_models, sigma, seed, dp)
+
+
+def delta_total(rows: torch.Tensor, base: torch.Tensor, where: Shard) -> torch.Tensor:
+    """Plain FedAvg's fp64 total sum_i (rows_i - base) over every rank's clients: this rank's
+    ``ops.delta_sum`` (zeros without clients), ONE reduction."""
+    return where.reduce(ops.delta_sum(rows, base))
 
 
 FIXED_MAX_TERMS = 512
@@ -215,15 +229,31 @@ def fedavg_clipped(global_state: torch.Tensor, finals: torch.Tensor, clip, eta: 
     Returns (factors [n], norms [n])."""
     where = where or Shard(finals.shape[0])
     rows, base = finals[:, :n_update], global_state[:n_update]
-    dev, idx = base.device, where.idx
-    sq_l, mx_l = ops.delta_stats(rows, base) if idx else (None, None)
-    sq = where.sum_rows(sq_l, (), torch.float64, dev)
+    sq, mx_l = delta_norms(rows, base, where)
     factors, _ = clip_factors(sq, clip)
-    E = fixed_exponent(where.reduce_max(max_abs(mx_l)), where.n)
-    part = clipped_part(rows, base, factors[idx].to(dev), E) if idx else wsum_zero(n_update, E, dev)
-    total = where.reduce(part)
-    ops.add_noise_scaled(base, total if E is None else fixed_decode(total, E), eta / no_models, sigma, seed, dp)
+    total = clipped_total(rows, base, factors, mx_l, where)
+    ops.add_noise_scaled(base, total, eta / no_models, sigma, seed, dp)
     return [float(x) for x in factors], [float(x) for x in sq.double().cpu().sqrt()]
+
+
+def delta_norms(rows: torch.Tensor, base: torch.Tensor, where: Shard) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(squared update norms of all n clients, fp64 [n]; max |delta| of this rank's clients, None
+    without any): one fused pass over this rank's rows (``ops.delta_stats``), ONE reduction."""
+    sq_l, mx_l = ops.delta_stats(rows, base) if where.idx else (None, None)
+    return where.sum_rows(sq_l, (), torch.float64, base.device), mx_l
+
+
+def clipped_total(rows: torch.Tensor, base: torch.Tensor, factors: torch.Tensor, mx_l: Optional[torch.Tensor],
+                  where: Shard) -> torch.Tensor:
+    """The fp64 total sum_i factors_i (rows_i - base) over every rank's clients, through the
+    fixed-point limbs (ONE max of a host float for the grid, ONE reduction of the [2, L] int64
+    limbs, decoded; fp64 partials if an update is not finite).  ``factors``: fp64 [n] on the host;
+    ``mx_l``: :func:`delta_norms`'s."""
+    dev, idx, L = base.device, where.idx, base.numel()
+    E = fixed_exponent(where.reduce_max(max_abs(mx_l)), where.n)
+    part = clipped_part(rows, base, factors[idx].to(dev), E) if idx else wsum_zero(L, E, dev)
+    total = where.reduce(part)
+    return total if E is None else fixed_decode(total, E)
 
 
 def krum_scores(D: torch.Tensor, f: int) -> torch.Tensor:
@@ -352,6 +382,49 @@ def fedavg_rlr(global_state: torch.Tensor, finals: torch.Tensor, theta: int, eta
     den = float(max(1, n_update))
     c = counts.cpu().tolist()
     return [float(a) / den for a, _ in c], [float(d) / den for _, d in c], int(flipped)
+
+
+def sparse_count(n_update: int, frac) -> int:
+    """The number k of coordinates a SparseFed round keeps: ``max(1, floor(sparse_topk *
+    n_update))`` (never more than ``n_update``), on the host, the same on every rank."""
+    f = C.check_sparse_topk(frac)
+    if f is None:
+        raise ValueError("sparse_count: sparse_topk is not set")
+    return min(int(n_update), max(1, int(math.floor(f * n_update))))
+
+
+def key_value(T: int) -> float:
+    """The magnitude whose select key (``ops.topk_threshold``) is ``T``."""
+    return float(torch.tensor(int(T), dtype=torch.int64).view(torch.float64))
+
+
+def fedavg_sparse(global_state: torch.Tensor, finals: torch.Tensor, k: int, clip, resid: torch.Tensor, eta: float,
+                  no_models: int, n_update: int, where: Optional[Shard] = None
+                  ) -> Tuple[List[float], List[float], int, float]:
+    """In-place SparseFed round over this rank's ``finals`` [len(idx), S]: the fp64 total of the
+    clients' updates (``clip`` None: plain FedAvg's, :func:`delta_total`; else each update clipped
+    as in :func:`fedavg_clipped`, :func:`clipped_total`) is added into the error-feedback residual
+    ``resid`` (fp64 [n_update], in place); the ``k`` largest-magnitude coordinates of the residual
+    (and every tie at the k-th) are applied, ``w += (eta / no_models) * resid``, and zeroed there;
+    every other coordinate of ``w`` is left untouched and stays in ``resid`` (``ops.topk_threshold``,
+    ``ops.topk_apply``).  The per-client norms always come from ``ops.delta_stats`` (ONE reduction
+    of [n] fp64); the total costs what the rule it borrows costs.  Every rank holds ``resid``
+    redundantly and selects and applies redundantly on the reduced total: no further collective,
+    the same bits at any world size.  ONE host read, after the apply is enqueued.  Returns (factors
+    [n], norms [n], kept m, the threshold magnitude)."""
+    where = where or Shard(finals.shape[0])
+    rows, base = finals[:, :n_update], global_state[:n_update]
+    sq, mx_l = delta_norms(rows, base, where)
+    if clip is None:
+        factors = torch.ones(where.n, dtype=torch.float64)
+        total = delta_total(rows, base, where)
+    else:
+        factors, _ = clip_factors(sq, clip)
+        total = clipped_total(rows, base, factors, mx_l, where)
+    sel = ops.topk_threshold(resid, total, k)
+    ops.topk_apply(base, resid, sel, eta / no_models)
+    T, m = sel.tolist()
+    return [float(x) for x in factors], [float(x) for x in sq.double().cpu().sqrt()], int(m), key_value(T)
 
 
 def _weiszfeld(avg, dists, alphas: torch.Tensor, maxiter: int, eps: float, ftol: float, poll: int = 0):

@@ -175,6 +175,8 @@ class Server:
     def _init_model(self) -> None:
         p = self.params
         self.counter = 0
+        # SparseFed's error-feedback residual (fp64 [n_upd], allocated by the first sparse_topk round)
+        self.sparse_residual: Optional[torch.Tensor] = None
         if p["resumed_model"]:
             path = os.path.join(p["save_dir"], str(p["resumed_model_name"]))
             if not os.path.exists(path):
@@ -190,6 +192,8 @@ class Server:
             if aux is not None:
                 ckpt.restore_rng(aux["rng"], self.wl.py_rng, self.wl.np_rng)
                 self._fg_aux = aux.get("foolsgold")
+                if aux.get("sparse_residual") is not None:     # (every rank: the residual is held redundantly)
+                    self.sparse_residual = aux["sparse_residual"].to(self.device, torch.float64)
         else:
             flat = self.spec.init_flat(int(p["seed"]))
             self.start_epoch = int(p.get("start_epoch") or 1)
@@ -368,9 +372,13 @@ class Server:
                 # fail fast: a non-finite global model poisons every later round
                 raise FloatingPointError(f"round {epoch}: aggregated global model is not finite "
                                          f"(aggregation={p['aggregation_methods']})")
+        # the residual as this round left it, for the round's checkpoint (written in _finish, when
+        # a pipelined next round may already have moved it on)
+        saves = self.write and p["save_model"] and p.sparse_topk is not None and self.sparse_residual is not None
         return {"epoch": epoch, "plan": plan, "bank": bank, "cstats": cstats, "t0": st["t0"],
                 "clients_on_rank": st["clients_on_rank"], "phases": self.timer.reset(), "early": early,
-                "comm_bytes": self.d.take_bytes()}
+                "comm_bytes": self.d.take_bytes(),
+                "sparse_residual": self.sparse_residual.clone() if saves else None}
 
     def _train_half(self, epoch: int, evaluate: bool = True) -> Dict[str, Any]:
         return self._train_end(self._train_begin(epoch, evaluate))
@@ -438,7 +446,7 @@ class Server:
             comm[k] = comm.get(k, 0) + v
         t_io = time.perf_counter()
         summary = self._record(pend["plan"], res, pend["cstats"])
-        self._save_model(pend["epoch"], summary["val_loss"], pend["bank"][0])
+        self._save_model(pend["epoch"], summary["val_loss"], pend["bank"][0], pend.get("sparse_residual"))
         self.csv.save(bool(p["is_poison"]))
         now = time.perf_counter()
         phases = dict(pend["phases"])
@@ -666,6 +674,18 @@ class Server:
             *cols, flipped = agg.fedavg_rlr(g, finals, p.rlr_threshold, eta, no_models, *tail, where)
             log.info(f"[rlr agg] theta: {size}  n: {n}  flipped: {flipped}/{n_upd} ({flipped / max(1, n_upd):.4f})  "
                      f"agree share (* adversary): {starred(cols[0])}")
+        elif key == "sparse_topk":
+            if self.sparse_residual is None:           # (first SparseFed round, or an .aux without one)
+                self.sparse_residual = torch.zeros(n_upd, dtype=torch.float64, device=self.device)
+            k, clip = agg.sparse_count(n_upd, p.sparse_topk), p.sparse_clip
+            *cols, kept, thr = agg.fedavg_sparse(g, finals, k, clip, self.sparse_residual, eta, no_models,
+                                                 n_upd, where)
+            clipped = ""
+            if clip is not None:
+                bound = agg.clip_bound(cols[1], clip)
+                clipped = f"  C: {bound}  clipped: {sum(v > bound for v in cols[1])}/{n}"
+            log.info(f"[sparse agg] k: {k}/{n_upd}  kept: {kept}  threshold: {thr}{clipped}  "
+                     f"residual norm: {float(torch.linalg.vector_norm(self.sparse_residual))}")
         elif method == C.AGGR_MEAN:
             agg.fedavg(g, finals, eta, no_models, *tail, where)
         elif method == C.AGGR_GEO_MED:
@@ -831,7 +851,8 @@ class Server:
             out["val_loss"] = out.get("global_loss")
         return out
 
-    def _save_model(self, epoch: int, val_loss: Optional[float], state: Optional[torch.Tensor] = None) -> None:
+    def _save_model(self, epoch: int, val_loss: Optional[float], state: Optional[torch.Tensor] = None,
+                    sparse_residual: Optional[torch.Tensor] = None) -> None:
         p = self.params
         if not (self.write and p["save_model"]):
             return
@@ -841,6 +862,8 @@ class Server:
         ckpt.save_checkpoint(name, self.spec, state, epoch, float(p["lr"]), self.counter)
         aux = {"rng": ckpt.rng_state(self.wl.py_rng, self.wl.np_rng), "foolsgold": self.fg.state(),
                "epoch": int(epoch)}
+        if sparse_residual is not None:      # (sparse_topk runs only: other runs' .aux keep their keys)
+            aux["sparse_residual"] = sparse_residual.detach().to("cpu", torch.float64)
         ckpt.save_aux(name + ".aux", aux)
         if epoch in list(p["save_on_epochs"] or []):
             log.info(f"Saving model on epoch {epoch}")

@@ -78,6 +78,12 @@ _SIGS = {
     "dba_delta_sum_votes": [_P, _LL, _I, _P, _LL, _P, _P, _P],
     "dba_vote_agreement": [_P, _LL, _I, _P, _P, _I, _LL, _P, _P, _P],
     "dba_rlr_apply": [_P, _P, _P, _I, _LL, _F, _F, _U, _I, _P, _P, _P],
+    # SparseFed: radix select of the k-th largest |residual| and the sparse apply (csrc/kernels/topk.hip)
+    "dba_topk_select_blocks": [_LL],
+    "dba_topk_apply_blocks": [_LL],
+    "dba_topk_ws_words": [],
+    "dba_topk_select": [_P, _P, _LL, _LL, _P, _P, _P],
+    "dba_topk_apply": [_P, _P, _P, _LL, _F, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
@@ -1520,6 +1526,46 @@ def rlr_apply(dst, total, votes, theta, coef, sigma, seed, noise):
     _call("dba_rlr_apply", dst.data_ptr(), total.data_ptr(), votes.data_ptr(), theta, L, float(coef), float(sigma),
           int(seed) & 0xFFFFFFFF, int(bool(noise)), flipped.data_ptr(), part.data_ptr(), _stream())
     return flipped
+
+
+def topk_workspace(device) -> Tensor:
+    """The int64 workspace of :func:`topk_threshold` (topk.hip: the passes' histograms and the
+    select's running state).  It needs no initialisation and carries nothing between calls."""
+    return torch.empty(int(_L.dba_topk_ws_words()), dtype=torch.int64, device=device)
+
+
+def topk_threshold(resid, total, k, ws=None):
+    """``resid += total`` in place, then ``sel`` int64 [2] on the device = (T, m): the k-th largest
+    key of ``resid`` (its bits with the sign cleared, as an integer) and the number of keys >= T
+    (topk.hip: an 8 x 8-bit radix select, the histograms integer adds, no host read; the first
+    pass does the addition).  Both entries are filled by this call's launches, m from the last
+    histogram; :func:`topk_apply` rewrites ``sel[1]`` with what it applied, the same m.  ``ws``: a
+    :func:`topk_workspace` to reuse (default: a fresh one)."""
+    L, k = _ref.topk_check(resid, total, k)
+    assert resid.is_cuda and resid.is_contiguous() and total.device == resid.device
+    sel = torch.zeros(2, dtype=torch.int64, device=resid.device)
+    if L == 0:
+        return sel
+    total = total.reshape(-1).contiguous()
+    ws = topk_workspace(resid.device) if ws is None else ws
+    assert ws.dtype == torch.int64 and ws.numel() >= int(_L.dba_topk_ws_words()) and ws.is_contiguous()
+    _call("dba_topk_select", resid.data_ptr(), total.data_ptr(), L, k, sel.data_ptr(), ws.data_ptr(), _stream())
+    return sel
+
+
+def topk_apply(dst, resid, sel, coef):
+    """Where ``key(resid) >= sel[0]``: ``dst += (float)(resid * (double)(float)coef)`` (the bits of
+    ``add_noise_scaled``, noise off) and ``resid = +0.0``; elsewhere neither is written (topk.hip
+    topk_apply_kernel).  ``sel[1]`` is rewritten with the number of coordinates applied (per-block
+    integer partials finalised in a fixed order): the m :func:`topk_threshold` left there."""
+    L = _ref.topk_apply_check(dst, resid, sel)
+    assert dst.is_cuda and dst.is_contiguous() and resid.is_contiguous() and sel.is_contiguous()
+    assert resid.device == dst.device and sel.device == dst.device
+    if L == 0:
+        return
+    part = torch.empty(int(_L.dba_topk_apply_blocks(L)), dtype=torch.int64, device=dst.device)
+    _call("dba_topk_apply", dst.data_ptr(), resid.data_ptr(), sel.data_ptr(), L, float(coef), part.data_ptr(),
+          _stream())
 
 
 def gram(feats):

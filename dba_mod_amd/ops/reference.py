@@ -764,6 +764,68 @@ def rlr_apply(dst: Tensor, total: Tensor, votes: Tensor, theta: int, coef: float
     return flipped
 
 
+TOPK_ABS_MASK = 0x7FFFFFFFFFFFFFFF
+
+
+def topk_keys(resid: Tensor) -> Tensor:
+    """The select keys of SparseFed: the bits of the fp64 ``resid`` with the sign bit cleared, as
+    (non-negative) int64.  Integer order is magnitude order: -0 and +0 are 0, denormals order, inf
+    ranks above every finite value and a NaN above inf, by payload."""
+    return resid.view(torch.int64) & TOPK_ABS_MASK
+
+
+def topk_check(resid: Tensor, total: Tensor, k) -> Tuple[int, int]:
+    """(L, k) of :func:`topk_threshold`, checked the same way on every backend: fp64 vectors of one
+    length, ``k`` an integer (a bool or a float is a ValueError) with 1 <= k <= L unless L = 0."""
+    assert resid.dim() == 1 and resid.dtype == torch.float64 and total.dtype == torch.float64
+    assert total.numel() == resid.numel(), (total.numel(), resid.numel())
+    L = resid.numel()
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"topk: k {k!r}: expected an integer")
+    if L and not 1 <= k <= L:
+        raise ValueError(f"topk: k {k} needs 1 <= k <= L = {L}")
+    return L, k
+
+
+def topk_apply_check(dst: Tensor, resid: Tensor, sel: Tensor) -> int:
+    assert dst.dim() == 1 and dst.dtype == torch.float32 and resid.dim() == 1 and resid.dtype == torch.float64
+    assert resid.numel() == dst.numel(), (resid.numel(), dst.numel())
+    assert sel.dtype == torch.int64 and sel.numel() == 2
+    return dst.numel()
+
+
+def topk_threshold(resid: Tensor, total: Tensor, k: int, ws: Optional[Tensor] = None) -> Tensor:
+    """SparseFed's select (topk.hip is the GPU form): ``resid += total`` in place (fp64 [L]), then
+    ``sel`` int64 [2] on the vectors' device = (T, m) with T the k-th largest of :func:`topk_keys`
+    and m the number of keys >= T (m >= k, more only on ties at T; T = 0 and m = L when fewer than k
+    keys are non-zero).  Both entries are filled here, without a host sync; :func:`topk_apply`
+    rewrites ``sel[1]`` with the number of coordinates it applied, which is the same m.  1 <= k <=
+    L or a ValueError; L = 0 gives (0, 0).  ``ws``: a workspace the GPU form can reuse (unused
+    here)."""
+    L, k = topk_check(resid, total, k)
+    if L == 0:
+        return torch.zeros(2, dtype=torch.int64, device=resid.device)
+    resid += total.reshape(-1)
+    keys = topk_keys(resid)
+    T = torch.sort(keys).values[L - k]
+    return torch.stack([T, (keys >= T).sum()])
+
+
+def topk_apply(dst: Tensor, resid: Tensor, sel: Tensor, coef: float) -> None:
+    """SparseFed's sparse update, in place: where ``topk_keys(resid) >= sel[0]``, ``dst +=
+    (float)(resid * (double)(float)coef)`` (the update of :func:`add_noise_scaled` with noise off,
+    at the fp32 coefficient the kernels take) and ``resid = +0.0``; elsewhere ``dst`` keeps its
+    bits (a ``-0.0f`` stays ``-0.0f``) and ``resid`` its value.  ``sel[1]`` is rewritten with the
+    number of coordinates applied."""
+    if topk_apply_check(dst, resid, sel) == 0:
+        return
+    kept = topk_keys(resid) >= sel[0]
+    c = torch.tensor(float(coef), dtype=torch.float32, device=dst.device).double()
+    dst.copy_(torch.where(kept, dst + (resid * c).to(dst.dtype), dst))
+    resid.masked_fill_(kept, 0.0)
+    sel[1] = kept.sum()
+
+
 def gram(feats: Tensor) -> Tensor:
     """F F^T in float64 (K15)."""
     f = feats.double()

@@ -415,6 +415,56 @@ def _bench_rlr(name, n, S, theta, reps, dev):
     return out
 
 
+# SparseFed (topk.hip): the CIFAR model's aggregated entries, k = 5 % as in configs/cifar_sparse.yaml
+TOPK = [("topk.cifar", 2_802_430, 0.05)]
+
+
+def _bench_topk(name, L, frac, reps, dev):
+    """The radix select (with the residual addition in its first pass) and the sparse apply on a
+    residual that a round's total is added into before every select, against the ``ops.reference``
+    torch path on the same device (``torch.sort`` of the keys: timed eagerly) and checked to give
+    its bits, and ``add_noise_scaled`` (plain FedAvg's dense update) at the same L for scale.  The
+    apply's steady state needs the select before it (a second apply at the same threshold finds
+    nothing to keep), so the pair is timed and ``apply_us`` is the pair minus the select.  The
+    select must move L * 24 bytes in its first pass and L * 8 in each of the other seven: GB/s
+    counts those L * 80."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    k = max(1, int(L * frac))
+    total = 0.01 * torch.randn(L, device=dev, dtype=torch.float64)
+    total[::7] = 0.0
+    base = torch.randn(L, device=dev)
+    coef = 0.1 / 10
+    ra, rb = (torch.zeros(L, dtype=torch.float64, device=dev) for _ in range(2))
+    da, db = base.clone(), base.clone()
+    ws = H.topk_workspace(dev)
+    for _ in range(3):                                            # three rounds: the residual carries over
+        sa, sb = H.topk_threshold(ra, total, k, ws=ws), R.topk_threshold(rb, total, k)
+        assert torch.equal(sa, sb) and torch.equal(ra, rb)
+        H.topk_apply(da, ra, sa, coef)
+        R.topk_apply(db, rb, sb, coef)
+        assert torch.equal(sa, sb) and torch.equal(ra, rb) and torch.equal(da, db)
+    out = {"shape": name, "L": L, "k": k, "kept": int(sa[1])}
+
+    def pair(o, resid, dst):
+        o.topk_apply(dst, resid, o.topk_threshold(resid, total, k), coef)
+
+    resid, dst = ra.clone(), base.clone()
+    t_pair = _time(lambda: pair(H, resid, dst), reps)
+    t_select = _time(lambda: H.topk_threshold(resid, total, k, ws=ws), reps)
+    t_noise = _time(lambda: H.add_noise_scaled(dst, total, coef, 0.0, 1, False), reps)
+    resid, dst = ra.clone(), base.clone()
+    r_pair = _time_eager(lambda: pair(R, resid, dst), reps)
+    r_select = _time_eager(lambda: R.topk_threshold(resid, total, k), reps)
+    out.update({"select_us": round(t_select * 1e6, 1), "select_GBps": round(L * 80 / t_select / 1e9, 1),
+                "apply_us": round((t_pair - t_select) * 1e6, 1), "select_apply_us": round(t_pair * 1e6, 1),
+                "select_reference_us": round(r_select * 1e6, 1),
+                "apply_reference_us": round((r_pair - r_select) * 1e6, 1),
+                "select_apply_reference_us": round(r_pair * 1e6, 1),
+                "add_noise_scaled_us": round(t_noise * 1e6, 1)})
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -455,6 +505,10 @@ def main(argv=None) -> int:
     for name, n, S, theta in RLR:
         if args.only in name:
             rows.append(_bench_rlr(name, n, S, theta, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, L, frac in TOPK:
+        if args.only in name:
+            rows.append(_bench_topk(name, L, frac, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
