@@ -132,9 +132,13 @@ _DEFAULTS: Dict[str, Any] = {
     # by the sum of its n - f - 2 smallest squared distances to the other clients' final states and
     # the m best-scored clients are averaged.  krum_f: None = off; an integer >= 0 = f, the number
     # of Byzantine clients tolerated per round (needs n >= 2 f + 3).  krum_m: None = n - f
-    # (Multi-Krum); an integer in 1 .. n - f = m (1 is the original Krum)
+    # (Multi-Krum); an integer in 1 .. n - f = m (1 is the original Krum).  krum_bulyan: None / false =
+    # Multi-Krum; true = Bulyan (El Mhamdi, Guerraoui and Rouault, ICML 2018) with f = krum_f: Krum
+    # iterated n - 2 f times picks the clients, then per coordinate the n - 4 f of their values closest
+    # to the median are averaged (needs n >= 4 f + 3; not with krum_m)
     "krum_f": None,
     "krum_m": None,
+    "krum_bulyan": None,
     # coordinate-wise trimmed mean / median (aggregation "mean" only; Yin et al., ICML 2018): per
     # coordinate the k smallest and k largest of the n client values are dropped and the rest
     # averaged.  None = off; an integer k >= 1 (needs n >= 2 k + 1); "median" = k = (n - 1) // 2,
@@ -231,6 +235,11 @@ class Params(dict):
     def krum_m(self) -> Optional[int]:
         """The checked ``krum_m``: None (m = n - f) or m >= 1."""
         return check_krum_int("krum_m", self.get("krum_m"), 1)
+
+    @property
+    def krum_bulyan(self) -> Optional[bool]:
+        """The checked ``krum_bulyan``: None (Multi-Krum; ``false`` reads as None) or True (Bulyan)."""
+        return check_krum_bulyan(self.get("krum_bulyan"))
 
     @property
     def trim_k(self) -> Any:
@@ -334,6 +343,34 @@ def check_krum_sizes(n: int, f: int, m: Optional[int], what: str = "n") -> int:
     return m
 
 
+def check_krum_bulyan(v: Any) -> Optional[bool]:
+    """None for None / False (Multi-Krum), True for True (Bulyan); anything else is an error."""
+    if v is None or v is False:
+        return None
+    if v is True:
+        return True
+    raise ValueError(f"krum_bulyan {v!r}: expected None, false or true")
+
+
+def check_bulyan_sizes(n: int, f: int, what: str = "n") -> int:
+    """Bulyan's inequality for n clients: n >= 4 f + 3 (so the n - 2 f clients that iterated Krum
+    selects leave beta = n - 4 f >= 3 values per coordinate, and every Krum iteration but the
+    clamped last ones scores at least one neighbour).  Returns theta = n - 2 f."""
+    if n < 4 * f + 3:
+        raise ValueError(f"krum_bulyan with krum_f {f} needs {what} >= 4 f + 3 = {4 * f + 3} (got {n})")
+    return n - 2 * f
+
+
+def krum_option_sizes(p: "Params", n: int, what: str = "n") -> int:
+    """The Krum option's inequalities for n clients: Multi-Krum's (returns m) or, with
+    ``krum_bulyan``, Bulyan's (returns theta; ``krum_m`` has no meaning there)."""
+    if p.krum_bulyan:
+        if p.krum_m is not None:
+            raise ValueError("krum_bulyan cannot be combined with krum_m (Bulyan selects n - 2 f clients)")
+        return check_bulyan_sizes(n, p.krum_f, what)
+    return check_krum_sizes(n, p.krum_f, p.krum_m, what)
+
+
 TRIM_MEDIAN = "median"
 
 
@@ -393,7 +430,7 @@ class MeanOption(NamedTuple):
 # in the order ``Server._aggregate`` looks for them; at most one is set
 MEAN_OPTIONS = (
     MeanOption("clip_norm", (), False, None),
-    MeanOption("krum_f", ("krum_m",), True, lambda p, n, what: check_krum_sizes(n, p.krum_f, p.krum_m, what)),
+    MeanOption("krum_f", ("krum_m", "krum_bulyan"), True, krum_option_sizes),
     MeanOption("trim_k", (), True, lambda p, n, what: check_trim_sizes(n, p.trim_k, what)),
     MeanOption("rlr_threshold", (), False, lambda p, n, what: check_rlr_sizes(n, p.rlr_threshold, what)),
     MeanOption("sparse_topk", ("sparse_clip",), False, None),

@@ -5,7 +5,7 @@ round's n client rows live is an argument: the rules whose sums decompose over c
 ``clip_norm``, ``rlr_threshold``, distributed RFA) take this rank's rows ``finals [len(idx), S]`` and
 a :class:`Shard` (the positions ``idx`` of those rows among the n, a sum and a max over the ranks;
 default: every row here, identity reductions); the rules that read every row (``krum_f``,
-``trim_k``) take the server's gathered snapshot bank and the clients' slots ``row_idx`` and read
+``krum_bulyan``, ``trim_k``) take the server's gathered snapshot bank and the clients' slots ``row_idx`` and read
 the rows in place.  Every rank applies the identical update redundantly, so no broadcast is
 needed and every rank ends the round with a bit-identical global model.  A rule returns what the
 server records: the two ``weight_result.csv`` columns (and what its log line needs).
@@ -27,6 +27,14 @@ server records: the two ``weight_result.csv`` columns (and what its log line nee
   crowd are dropped and the rest averaged.  The [n, n] squared distances between the final states
   come from one fused HIP pass (``ops.pairwise_sq_dists``: fp64 differences, no atomics, a pair's
   bits independent of the other rows); scores and selection are host fp64 arithmetic.
+* :func:`fedavg_bulyan` / :func:`bulyan_select` — Bulyan (config ``krum_f`` with ``krum_bulyan``;
+  El Mhamdi, Guerraoui and Rouault, ICML 2018; not in the reference): Krum iterated on the same
+  distance matrix picks theta = n - 2 f clients one at a time (host fp64 arithmetic), then per
+  coordinate the beta = theta - 2 f of their values closest to the coordinate's lower median are
+  averaged.  The second stage is one fused HIP pass over the selected rows where they lie
+  (``ops.bulyan_delta_sum``: the sort in registers, the window found without a dynamic index, its
+  ranks added in ascending order in fp64), which also counts, per selected client, the
+  coordinates at which it was kept.
 * :func:`fedavg_trimmed` / :func:`trim_count` — coordinate-wise trimmed mean / median (config
   ``trim_k``; Yin et al., ICML 2018; not in the reference): per coordinate the k smallest and k
   largest client values are dropped and the rest averaged; no per-client decision.  One fused HIP
@@ -310,6 +318,74 @@ def fedavg_krum(global_state: torch.Tensor, finals: torch.Tensor, f: int, m: Opt
     total = ops.delta_sum(selected[:, :n_update], global_state[:n_update])
     ops.add_noise_scaled(global_state[:n_update], total, eta / len(sel), sigma, seed, dp)
     return [1.0 if i in sel else 0.0 for i in range(n)], [float(x) for x in scores]
+
+
+def bulyan_select(D: torch.Tensor, f: int) -> Tuple[List[int], List[float]]:
+    """Bulyan's first stage, iterated Krum on the [n, n] squared-distance matrix: (the selected
+    clients in selection order, scores [n]).  Non-finite entries of D count as +inf, as in
+    :func:`krum_scores`.  With the remaining set R = all n clients, until theta = n - 2 f are
+    selected: r = |R|, k = max(1, r - f - 2) (the clamp serves the last iterations, where r - f - 2 <
+    1; a lone last client has no neighbour and scores 0); score_i, i in R, is the sum in ascending
+    order of the k smallest D[i][j], j in R, j != i; the smallest score wins, ties to the lower
+    index; a winner whose score is not finite stops the selection; otherwise it leaves R, joins
+    the selection and keeps its score of that moment.  A client never selected reports its score
+    from the last iteration that ran.  Fewer than 2 f + 1 selected (the second stage's minimum) is
+    an error.  Host fp64 arithmetic on a matrix every rank holds with the same bits."""
+    D = D.detach().double().cpu()
+    n = D.shape[0]
+    if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+        raise ValueError(f"bulyan: f = {f!r} is not an integer >= 0")
+    theta = n - 2 * f
+    if theta < 2 * f + 1:
+        raise ValueError(f"bulyan: n = {n} clients need n >= 4 f + 1 (f = {f}) to select 2 f + 1")
+    rows = torch.where(torch.isfinite(D), D, torch.full_like(D, math.inf)).tolist()
+    remaining = list(range(n))
+    scores = [math.inf] * n
+    selected: List[int] = []
+    while len(selected) < theta:
+        k = max(1, len(remaining) - f - 2)
+        for i in remaining:
+            s = 0.0
+            for v in sorted(rows[i][j] for j in remaining if j != i)[:k]:
+                s += v
+            scores[i] = s
+        win = min(remaining, key=lambda i: (scores[i], i))
+        if not math.isfinite(scores[win]):
+            break
+        remaining.remove(win)
+        selected.append(win)
+    if len(selected) < 2 * f + 1:
+        raise RuntimeError(f"bulyan: only {len(selected)} of {n} clients have a finite score, fewer than "
+                           f"2 f + 1 = {2 * f + 1} (the other client states are non-finite)")
+    return selected, scores
+
+
+def fedavg_bulyan(global_state: torch.Tensor, finals: torch.Tensor, f: int, eta: float, dp: bool, sigma: float,
+                  seed: int, n_update: int, row_idx: Optional[Sequence[int]] = None
+                  ) -> Tuple[List[float], List[float], List[int]]:
+    """In-place Bulyan of the n clients' final states: the rows ``row_idx`` of ``finals`` (the
+    server's gathered snapshot bank, read in place) or all of ``finals`` [n, S]; n >= 4 f + 3.  The
+    squared distances between the states over the ``n_update`` leading entries
+    (``ops.pairwise_sq_dists``), :func:`bulyan_select` (t clients, normally n - 2 f), then over the
+    selected rows in client order, per coordinate, the beta = t - 2 f values closest to the lower
+    median (``ops.bulyan_delta_sum``: one fused HIP pass) and ``w += (eta / beta) * total (+
+    noise)``.  Every rank holds every row and computes the same bits redundantly: no reduction.
+    Returns (kept share [n], scores [n], the selected clients in selection order): the fraction of
+    the aggregated coordinates at which each client's value was inside the window, 0.0 for a
+    client the first stage dropped."""
+    n = finals.shape[0] if row_idx is None else len(row_idx)
+    C.check_bulyan_sizes(n, f, "the round's clients")
+    D = ops.pairwise_sq_dists(finals[:, :n_update], row_idx)
+    order, scores = bulyan_select(D, f)
+    sel = sorted(order)
+    total, kept, _ = ops.bulyan_delta_sum(finals[:, :n_update], global_state[:n_update], f,
+                                          sel if row_idx is None else [row_idx[i] for i in sel])
+    ops.add_noise_scaled(global_state[:n_update], total, eta / (len(sel) - 2 * f), sigma, seed, dp)
+    den = float(max(1, n_update))
+    share = [0.0] * n
+    for i, v in zip(sel, kept.tolist()):
+        share[i] = float(v) / den
+    return share, [float(x) for x in scores], order
 
 
 def trim_count(n: int, trim_k) -> int:

@@ -543,7 +543,7 @@ class Server:
         Client snapshots stay on their owner rank.  Only the rows some other rank reads are
         broadcast from their owners: the snapshots of clients whose tests are image-sharded across ranks
         (the round's longest clients, or every client without early local tests) and, for
-        RFA in gather mode, for Multi-Krum and for the trimmed mean, the final states.  Aggregation itself reduces
+        RFA in gather mode, for Multi-Krum, Bulyan and the trimmed mean, the final states.  Aggregation itself reduces
         (``_aggregate``)."""
         S, P = self.spec.S, self.spec.P
         world, rank = self.d.world, self.d.rank
@@ -651,7 +651,8 @@ class Server:
         tail = (bool(p["diff_privacy"]), float(p["sigma"]), dp_seed, n_upd)
         option = C.mean_option(p) if method == C.AGGR_MEAN else None
         key = option.key if option is not None else None
-        # the rule's inequalities against the round's actual client count: Krum's m, the trim count k, theta
+        # the rule's inequalities against the round's actual client count: Krum's m (Bulyan's theta), the trim
+        # count k, theta
         size = option.sizes(p, n, "the round's clients") if option is not None and option.sizes else None
         cols: Optional[Tuple[List[float], List[float]]] = None      # the two weight_result.csv columns
 
@@ -662,6 +663,13 @@ class Server:
             cols = agg.fedavg_clipped(g, finals, p.clip_norm, eta, no_models, *tail, where)
             bound = agg.clip_bound(cols[1], p.clip_norm)
             log.info(f"[clip agg] C: {bound}  clipped: {sum(v > bound for v in cols[1])}/{n}  factors: {cols[0]}")
+        elif key == "krum_f" and p.krum_bulyan:
+            *cols, order = agg.fedavg_bulyan(g, bank, p.krum_f, eta, *tail, row_idx=slots)
+            chosen = [names[i] for i in order]
+            log.info(f"[bulyan agg] f: {p.krum_f}  theta: {size}  beta: {len(chosen) - 2 * p.krum_f}  "
+                     f"selected (in order): {chosen}  "
+                     f"adversaries selected: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}  "
+                     f"kept share (* adversary): {starred(cols[0])}")
         elif key == "krum_f":
             cols = agg.fedavg_krum(g, bank, p.krum_f, size, eta, *tail, row_idx=slots)
             chosen = [nm for nm, on in zip(names, cols[0]) if on]

@@ -72,6 +72,9 @@ _SIGS = {
     # coordinate-wise trimmed mean / median (csrc/kernels/trim.hip)
     "dba_coord_trim_blocks": [_LL],
     "dba_coord_trim": [_P, _LL, _P, _I, _P, _I, _LL, _P, _P, _P, _P],
+    # Bulyan's coordinate-wise median window (csrc/kernels/bulyan.hip)
+    "dba_coord_bulyan_blocks": [_LL],
+    "dba_coord_bulyan": [_P, _LL, _P, _I, _P, _I, _LL, _P, _P, _P, _P],
     # robust-learning-rate FedAvg: sign votes (csrc/kernels/rlr.hip)
     "dba_vote_agreement_blocks": [_LL],
     "dba_rlr_apply_blocks": [_LL],
@@ -1458,6 +1461,35 @@ def trimmed_delta_sum(buf, base, k, row_idx=None):
     counts = torch.empty(n, 2, dtype=torch.int64, device=buf.device)
     part = torch.empty(2 * n * int(_L.dba_coord_trim_blocks(L)), dtype=torch.int64, device=buf.device)
     _call("dba_coord_trim", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), k, L, total.data_ptr(),
+          counts.data_ptr(), part.data_ptr(), _stream())
+    return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
+
+
+BULYAN_MAX_ROWS = 64       # bulyan.hip kMaxRows
+
+
+def bulyan_delta_sum(buf, base, f, row_idx=None):
+    """(total fp64 [L], kept int64 [t], high int64 [t]) of Bulyan's coordinate-wise median window
+    over ``buf[row] - base`` (bulyan.hip): one fused pass over the rows where they lie (``row_idx``:
+    t row numbers into ``buf``, repeats allowed), each coordinate sorted in registers, the t - 2 f
+    ranks closest to the lower median added in ascending order in fp64; no atomics, bitwise run to
+    run.  More than 64 rows (or 2^31 coordinates) take the reference composition on the device."""
+    buf, rs, idx, t = _picked_rows("bulyan_delta_sum", buf, row_idx)
+    L = buf.shape[1]
+    assert base.dtype == torch.float32 and base.device == buf.device
+    assert base.numel() == L, (tuple(buf.shape), base.numel())
+    f = _ref.check_bulyan(t, f)
+    if t > BULYAN_MAX_ROWS or L >= 1 << 31:
+        return _ref.bulyan_delta_sum(buf, base, f, row_idx)
+    if t == 0 or L == 0:
+        return (torch.zeros(L, dtype=torch.float64, device=buf.device),
+                torch.zeros(t, dtype=torch.int64, device=buf.device),
+                torch.zeros(t, dtype=torch.int64, device=buf.device))
+    base = base.contiguous()
+    total = torch.empty(L, dtype=torch.float64, device=buf.device)
+    counts = torch.empty(t, 2, dtype=torch.int64, device=buf.device)
+    part = torch.empty(2 * t * int(_L.dba_coord_bulyan_blocks(L)), dtype=torch.int64, device=buf.device)
+    _call("dba_coord_bulyan", buf.data_ptr(), rs, _ptr(idx), t, base.data_ptr(), f, L, total.data_ptr(),
           counts.data_ptr(), part.data_ptr(), _stream())
     return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
 

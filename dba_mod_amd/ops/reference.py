@@ -687,6 +687,60 @@ def trimmed_delta_sum(buf: Tensor, base: Tensor, k: int, row_idx=None) -> Tuple[
     return total, kept, high
 
 
+def check_bulyan(t: int, f: int) -> int:
+    """Bulyan's f for t selected rows: an integer with 0 <= f and 2 f + 1 <= t (f = 0 when t = 0)."""
+    if isinstance(f, bool) or not isinstance(f, int) or f < 0 or (2 * f + 1 > t and not (t == 0 and f == 0)):
+        raise ValueError(f"bulyan_delta_sum: f = {f!r} needs 0 <= f <= (t - 1) // 2 (t = {t})")
+    return f
+
+
+def bulyan_delta_sum(buf: Tensor, base: Tensor, f: int, row_idx=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Bulyan's second stage (El Mhamdi, Guerraoui and Rouault, ICML 2018; bulyan.hip is the GPU
+    form): the coordinate-wise median window over the rows ``row_idx`` (t row numbers, repeats
+    allowed) or all of ``buf`` [R, L] fp32, ``base`` [L] fp32, ``0 <= f <= (t - 1) // 2``.  Per
+    coordinate the t values are sorted ascending in :func:`trimmed_delta_sum`'s order (every NaN
+    after +inf, -0 == +0): s_0 .. s_{t-1}.  With ``beta = t - 2 f``, ``m = (t - 1) // 2`` and ``med =
+    (double)s_m`` (the lower median) the window is the ranks ``a .. a + beta - 1``, where ``a`` is
+    the number of j in ``0 .. 2 f - 1`` with ``(double)s_{j+beta} - med < med - (double)s_j`` (fp64,
+    false when a side is NaN): the beta values closest to the median, ties to the lower one.
+    ``d_r = (double)s_r - (double)base`` and ``total = ((d_a + d_{a+1}) + ...) + d_{a+beta-1}``, one
+    fp64 rounding per addition, in ascending rank.  With ``lo = s_a`` and ``hi = s_{a+beta-1}`` a row
+    is low at a coordinate if ``v < lo``, high if ``v > hi`` or v is NaN and hi is not, kept
+    otherwise (rows tied with a threshold are all kept).  Returns (total fp64 [L], kept int64
+    [t], high int64 [t]).  Chunked over L: no [t, L] fp64."""
+    idx, t = _picked_rows(buf, row_idx)
+    L = buf.shape[1]
+    f = check_bulyan(t, f)
+    total = torch.zeros(L, dtype=torch.float64, device=buf.device)
+    kept = torch.zeros(t, dtype=torch.int64, device=buf.device)
+    high = torch.zeros(t, dtype=torch.int64, device=buf.device)
+    if t == 0:
+        return total, kept, high
+    beta, m = t - 2 * f, (t - 1) // 2
+    b = base.double()
+    for c0 in range(0, L, TRIM_CHUNK):
+        x = buf[:, c0:c0 + TRIM_CHUNK]
+        x = x if idx is None else x.index_select(0, idx)
+        s = torch.sort(x, dim=0).values                       # (NaN last)
+        med = s[m].double()
+        a = torch.zeros(s.shape[1], dtype=torch.int64, device=buf.device)
+        for j in range(2 * f):
+            a += (s[j + beta].double() - med) < (med - s[j].double())
+        bc = b[c0:c0 + TRIM_CHUNK]
+        lo = s.gather(0, a[None])
+        tot = lo[0].double() - bc
+        hi = lo
+        for r in range(1, beta):
+            hi = s.gather(0, (a + r)[None])
+            tot = tot + (hi[0].double() - bc)
+        total[c0:c0 + TRIM_CHUNK] = tot
+        is_low = x < lo
+        is_high = (x > hi) | (x.isnan() & ~hi.isnan())
+        kept += (~is_low & ~is_high).sum(1)
+        high += is_high.sum(1)
+    return total, kept, high
+
+
 RLR_CHUNK = 1 << 18
 
 

@@ -356,6 +356,45 @@ def _bench_trim(name, n, S, k, reps, dev):
             "fused_vs_composed_max_rel": max_rel}
 
 
+# Bulyan's median window (bulyan.hip): the 8 clients iterated Krum selects of a CIFAR round's 10, f = 1 as in
+# configs/cifar_bulyan.yaml
+BULYAN = [("bulyan.cifar", 8, 2_802_430, 1)]
+
+
+def _bench_bulyan(name, t, S, f, reps, dev, rounds=5):
+    """The fused median-window kernel over t final-state rows read where they lie in a 21-row
+    snapshot bank, against (a) ``trimmed_delta_sum`` over the same rows with k = f — the same loads
+    and the same sort, a symmetric window: the yardstick — and (b) ``delta_sum`` over the same
+    rows, the byte floor.  The three are timed in turn, ``rounds`` times over, in this process: the
+    median of each and its min .. max (the spread a difference has to leave to mean anything).
+    GB/s counts t * S * 4 bytes.  The bits are checked against the reference op first."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    bank = base[None] + 0.01 * torch.randn(21, S, device=dev)             # finals in the odd slots
+    slots = torch.arange(1, 2 * t + 1, 2, device=dev)
+    rows = bank[1:2 * t + 1:2]                                            # the same rows as a strided view
+    assert rows.shape[0] == t and torch.equal(rows, bank[slots])
+    total, kept, high = H.bulyan_delta_sum(rows, base, f)
+    rt, rk, rh = R.bulyan_delta_sum(bank, base, f, slots)
+    assert torch.equal(total, rt) and torch.equal(kept, rk) and torch.equal(high, rh)
+    off_trim = float((total != H.trimmed_delta_sum(rows, base, f)[0]).double().mean())
+    fns = {"bulyan": lambda: H.bulyan_delta_sum(rows, base, f), "trim": lambda: H.trimmed_delta_sum(rows, base, f),
+           "delta_sum": lambda: H.delta_sum(rows, base)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(_time(fn, reps))
+    b = t * S * 4
+    out = {"shape": name, "t": t, "S": S, "f": f, "rounds": rounds, "totals_off_the_trimmed_sum": round(off_trim, 4)}
+    for k, v in times.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        out.update({f"{k}_us": round(med * 1e6, 1), f"{k}_min_us": round(v[0] * 1e6, 1),
+                    f"{k}_max_us": round(v[-1] * 1e6, 1), f"{k}_GBps": round(b / med / 1e9, 1)})
+    return out
+
+
 # robust learning rate (rlr.hip): a CIFAR round's 10 final states, theta = 4 as in configs/cifar_rlr.yaml
 RLR = [("rlr.cifar", 10, 2_802_430, 4)]
 
@@ -501,6 +540,10 @@ def main(argv=None) -> int:
     for name, n, S, k in TRIM:
         if args.only in name:
             rows.append(_bench_trim(name, n, S, k, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, t, S, f in BULYAN:
+        if args.only in name:
+            rows.append(_bench_bulyan(name, t, S, f, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     for name, n, S, theta in RLR:
         if args.only in name:
