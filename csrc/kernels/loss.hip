@@ -336,6 +336,13 @@ __global__ __launch_bounds__(256) void head_rows_kernel(
     for (int k = 0; k < K; ++k) s = fmaf(lg[n * kHeadK + k], Wg[k * C + c], s);
     dpool[((long long)g * N + r0 + n) * C + c] = s;
   }
+  // the block's rows at and beyond nvalid: a zero gradient, as the unfused path's zero dlogits of
+  // padding rows give (avgpool_global_bwd copies every row of dpool)
+  const int nz = min(kHeadRows, N - r0) - nr;
+  for (int e = tid; e < nz * C; e += 256) {
+    const int n = nr + e / C, c = e % C;
+    dpool[((long long)g * N + r0 + n) * C + c] = 0.f;
+  }
 }
 
 // grid (column blocks of 64, replicas): the weight gradient dW[k][c] = sum over the valid rows

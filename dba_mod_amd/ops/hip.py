@@ -1226,7 +1226,15 @@ def head_train(x, w, b, labels, nvalid, dw, db, stats=None, slot=None, mean=True
     """The training head in two launches (loss.hip head_rows_kernel / head_fin_kernel): pooled = avgpool(x), logits =
     pooled W^T + b, softmax cross-entropy (mean over valid rows) + correct count (+ ``stats``
     slots), and its backward: ``dw`` / ``db`` overwritten for the active replicas, the pooled
-    features' gradient returned.  Returns (loss [G], correct [G], dpool [G, N, 1, 1, C])."""
+    features' gradient returned.  Returns (loss [G], correct [G], dpool [G, N, 1, 1, C]).
+
+    Contract for the rows at and beyond ``nvalid[g]``: their labels are -1 (the mean's divisor
+    counts the labels >= 0 of all N rows, as softmax_xent does) and their ``dpool`` rows are
+    zero, as the unfused path's (zero dlogits of padding rows): ``bn_finish(pool=dpool, nvalid)``
+    takes the valid rows only, but ``avgpool_global_bwd`` copies every row.  The internal pooled /
+    dlogits rows at and beyond ``nvalid[g]`` are NOT written (``torch.empty``) and never read.
+    ``dw`` / ``db`` of a replica with ``nvalid == 0`` are left untouched; a valid row with label -1
+    gets zero dlogits."""
     x = _act(x, _F32, "head input")
     G, N, H, W_, C = x.shape
     K = w.shape[1]
