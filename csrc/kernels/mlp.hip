@@ -98,6 +98,10 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
+// ReLU that passes a NaN on, as the reference's nn.ReLU does (fmaxf returns its other operand: a
+// NaN feature stopped at layer 1, the loss stayed finite and nan_flag unset while the NaN went
+// into W1 through the weight gradient); the same value as fmaxf(v, 0.f) for every other input
+__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
 __device__ __forceinline__ int tile_row(int r) { return (r & 3) + 8 * (r >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
 
 __global__ __launch_bounds__(kT) void mlp_train_kernel(const MlpArgs a) {
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(kT) void mlp_train_kernel(const MlpArgs a) {
         for (int r = 0; r < 16; ++r) {
           const int b = mt * 32 + tile_row(r);
           const bool keep = uniform01(seed, (uint32_t)(b * kH1 + j)) >= 0.5f;
-          s.a1T[j * kLD + b] = keep ? fmaxf(z[r] + bj, 0.f) * 2.0f : 0.f;
+          s.a1T[j * kLD + b] = keep ? relu_nan(z[r] + bj) * 2.0f : 0.f;
         }
       }
     }
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(kT) void mlp_train_kernel(const MlpArgs a) {
         for (int r = 0; r < 16; ++r) {
           const int b = mt * 32 + tile_row(r);
           const bool keep = uniform01(sd1, (uint32_t)(b * kH2 + j)) >= 0.5f;
-          s.a2T[j * kLD + b] = keep ? fmaxf(z[r] + bj, 0.f) * 2.0f : 0.f;
+          s.a2T[j * kLD + b] = keep ? relu_nan(z[r] + bj) * 2.0f : 0.f;
         }
       }
     }
