@@ -79,6 +79,16 @@ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t ctr) {
   return ((float)(hash2(seed, ctr) >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
 
+// ReLU that passes a NaN on, as the reference's torch.relu does (fmaxf returns its other operand,
+// so a NaN activation stopped at the first fused ReLU, the loss stayed finite and nan_flag unset);
+// the same value as fmaxf(v, 0.f) for every other input.  Every data-path ReLU uses it.  IEEE
+// 754-2019 maximum: one v_maximum3_f32 on gfx950, as cheap as the v_max_f32 it replaces (the
+// compare + select form was slower in the lazy-BN staging of the convs: ARCHITECTURE section 7).
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ void relu_nan4(float4& v) {
+  v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
@@ -129,3 +139,28 @@ static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #define DBA_LAUNCH_CHECK() return (int)hipGetLastError()
+
+// The conv family's last main-kernel launch of this process, written by each launcher on the host
+// (dba_xconv_last_launch, xconv_fwd.hip): the tests check that a shape reached the kernel they name.
+// One unsynchronised process-wide record: it is meaningful only when read right after a call, on
+// the thread that made it, with no other host thread launching convs (the tests' situation);
+// launches from several threads (autograd's, a side stream's) overwrite each other.
+//   kind                  tile          vec                    pre              form
+//   1 xconv_kernel        BN (columns)  staging vector 1/4/32  pre-split w      split-K: 0 none, 1 combined in the
+//                                                                               launch, 2 in-block slabs, 3 slabs + reduce
+//   2 xhalo_kernel        image width   Cs                     pre-split w      0
+//   3 ximg_kernel         image width   BN                     pre-split w      0
+//   4 ximg2_kernel        image width   BN                     1                0
+//   5 xstage16_kernel     16            64                     1                0
+//   6 xstem_kernel        Cout          Cin                    0                0
+//   7 xwgrad_kernel       Cout tile     staging vector 1/4     0                1 = a partial last slab
+//   8 xwgrad_halo_kernel  image width   4                      0                0
+//   9 xwgrad_stem_kernel  image width   1                      0                0
+// slabs: split-K slabs (1) or weight-gradient slabs Z (7-9), else 1;  nclass: parity classes of the
+// launch (1);  lazy: an operand formed while staging (LazyBN x / LazyGrad dy)
+struct XLast {
+  int kind, tile, vec, pre, form, slabs, nclass, lazy;
+};
+namespace xg {
+XLast& last_launch();
+}

@@ -98,10 +98,8 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-// ReLU that passes a NaN on, as the reference's nn.ReLU does (fmaxf returns its other operand: a
-// NaN feature stopped at layer 1, the loss stayed finite and nan_flag unset while the NaN went
-// into W1 through the weight gradient); the same value as fmaxf(v, 0.f) for every other input
-__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+// (relu_nan, common.hpp: with fmaxf a NaN feature stopped at layer 1, the loss stayed finite and
+// nan_flag unset while the NaN went into W1 through the weight gradient)
 __device__ __forceinline__ int tile_row(int r) { return (r & 3) + 8 * (r >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
 
 __global__ __launch_bounds__(kT) void mlp_train_kernel(const MlpArgs a) {

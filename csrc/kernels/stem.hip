@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void xstem_kernel(const StemArgs a) {
           const float4 r = *(const float4*)(a.res + o + c4 * 4);
           v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
         }
-        if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (a.relu) relu_nan4(v);
         vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
         *(float4*)(a.out + o + c4 * 4) = v;
         acc[c4 * 4] = v.x; acc[c4 * 4 + 1] = v.y; acc[c4 * 4 + 2] = v.z; acc[c4 * 4 + 3] = v.w;
@@ -148,6 +148,7 @@ int stem_go(const StemArgs& a, int G, hipStream_t st) {
   if (a.bf.mode && PIX % 32 != 0) return -100;
   const long long M = (long long)a.N * a.Ho * a.Wo;
   const dim3 grid((unsigned)ceil_div(M, PIX * ITER), G);
+  xg::last_launch() = XLast{6, COUT, CIN, 0, 0, 1, 1, 0};
   hipLaunchKernelGGL((xstem_kernel<KH, KW, CIN, COUT, CPT, ITER>), grid, dim3(256), 0, st, a);
   const int rc = (int)hipGetLastError();
   if (rc != 0 || !a.bf.mode) return rc;

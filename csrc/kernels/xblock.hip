@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int px = (r & 3) + 8 * (r >> 2) + 4 * hf;
-        const float v = in_img ? fmaxf(acc[i][r] + bias0, 0.f) : 0.f;
+        const float v = in_img ? relu_nan(acc[i][r] + bias0) : 0.f;
         smax = fmaxf(smax, v);
         Ct[(pr * kW + px) * kC + fr] = v;
         if (i > 0) res[i - 1][r] = v;
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int px = (r & 3) + 8 * (r >> 2) + 4 * hf;
-      const float v = in_img ? fmaxf(acc[i][r] + bias1, 0.f) : 0.f;
+      const float v = in_img ? relu_nan(acc[i][r] + bias1) : 0.f;
       vmax = fmaxf(vmax, v);
       Ct[(mr * kW + px) * kC + fr] = v;
     }
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float v = acc[i][r];
-      if constexpr (STEM) v = fmaxf(v + bias2 + res[i][r], 0.f);   // the residual from registers
+      if constexpr (STEM) v = relu_nan(v + bias2 + res[i][r]);   // the residual from registers
       Ct[((wid + 4 * i) * kW + (r & 3) + 8 * (r >> 2) + 4 * hf) * kC + fr] = v;
     }
   __syncthreads();
@@ -506,10 +506,10 @@ __global__ __launch_bounds__(256) void xblock_kernel(const XBArgs a) {
     if constexpr (!STEM) {
       const int c4 = (e % Q4) * 4;
       const float4 rv = *(const float4*)(res_g + e * 4);
-      v.x = fmaxf(v.x + b2[c4] + rv.x, 0.f);
-      v.y = fmaxf(v.y + b2[c4 + 1] + rv.y, 0.f);
-      v.z = fmaxf(v.z + b2[c4 + 2] + rv.z, 0.f);
-      v.w = fmaxf(v.w + b2[c4 + 3] + rv.w, 0.f);
+      v.x = relu_nan(v.x + b2[c4] + rv.x);
+      v.y = relu_nan(v.y + b2[c4 + 1] + rv.y);
+      v.z = relu_nan(v.z + b2[c4 + 2] + rv.z);
+      v.w = relu_nan(v.w + b2[c4 + 3] + rv.w);
     }
     omax = fmaxf(omax, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
     *(float4*)(out + e * 4) = v;

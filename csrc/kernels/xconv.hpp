@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256, KS ? 2 : XCONV_MINB) void xconv_kernel(const X
         const float4 sc = *(const float4*)&lzc[kq4], sh = *(const float4*)&lzc[512 + kq4];
         float4 v = ra[st][q];
         v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
-        if (a.lz_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (a.lz_relu) relu_nan4(v);
         if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
         split4h(v.x, v.y, v.z, v.w, hs.ma, sp);
       } else {
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256, KS ? 2 : XCONV_MINB) void xconv_kernel(const X
         const float4 rv = *(const float4*)(res + o + n);
         v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
       }
-      if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (relu) relu_nan4(v);
       if (bfm == 2) {   // backward: d = the gradient where the BN(+ReLU) output is > 0
         v = bnf_mask4(a.bf, g, o, n, v);
         *(float4*)&Ct[row * BN + cc] = v;
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256, KS ? 2 : XCONV_MINB) void xconv_kernel(const X
       float v = Ct[row * BN + cc];
       if (bias) v += bias[n];
       if (res) v += res[o + n];
-      if (relu) v = fmaxf(v, 0.f);
+      if (relu) v = relu_nan(v);
       vmax = fmaxf(vmax, fabsf(v));
       out[o + n] = v;
     }
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(256) void xsplitk_reduce_kernel(const float* __rest
     for (int z = 1; z < S; ++z) v += ws[z * zstride + base + e];
     if (bp) v += bp[e % Ncol];
     if (res) v += res[base + e];
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = relu_nan(v);
     vmax = fmaxf(vmax, fabsf(v));
     out[base + e] = v;
   }
@@ -585,6 +585,7 @@ int xconv_go(const XArgs& a, long long Mmax, int G, int nclass, hipStream_t st) 
   XArgs b = a;
   b.tiles_n = ceil_div(a.Ncol, BN);
   const dim3 grid((unsigned)(ceil_div(Mmax, BM) * b.tiles_n), G, nclass * a.splitk);
+  xg::last_launch() = XLast{1, BN, VEC, PW, KS ? 2 : a.splitk > 1 ? (a.sk_cnt ? 1 : 3) : 0, KS ? a.kslab : a.splitk, nclass, LZ};
   hipLaunchKernelGGL((xconv_kernel<BM, BN, WM, WN, VEC, PW, LZ, KS>), grid, dim3(256), 0, st, b);
   DBA_LAUNCH_CHECK();
 }

@@ -64,9 +64,10 @@ __global__ __launch_bounds__(256) void xtranspose_kernel(const XTBatch b, int sl
   }
 }
 
+constexpr int kMaxDgradStride = 2;   // the class tables below and XArgs::cls hold s * s <= 4 entries
 struct ClassGeom {
   int n;
-  XClass c[4];
+  XClass c[kMaxDgradStride * kMaxDgradStride];
 };
 
 // parity classes of a stride-s data gradient (see xtranspose_kernel for the weight order)
@@ -102,6 +103,7 @@ DBA_EXPORT int dba_xconv_dgrad(const float* dy, long long dy_gstride, const floa
                                long long ws_floats, int* sk_cnt, long long sk_cnt_n, const void* bnf, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if ((long long)N * Ho * Wo * Cout >= (1LL << 29)) return -103;   // 32-bit in-replica byte offsets
+  if (stride < 1 || stride > kMaxDgradStride) return -110;   // s * s parity classes: ClassGeom / XArgs::cls hold 4
   const ClassGeom cg = dgrad_classes(H, W, Cin, Cout, KH, KW, stride, pad);
   const int vec = (Cout % 4 == 0 && aligned16(dy) && aligned16(wt) && dy_gstride % 4 == 0 && wt_sstride % 4 == 0) ? 4 : 1;
   XArgs a{};
@@ -172,6 +174,8 @@ DBA_EXPORT int dba_xconv_dgrad(const float* dy, long long dy_gstride, const floa
 DBA_EXPORT int dba_xtranspose(const void* desc, int n, int slots, long long max_per, const int* nvalid,
                               void* stream) {
   const XTDesc* ds = (const XTDesc*)desc;
+  for (int i = 0; i < n; ++i)   // the class-packed order is only consumed by dba_xconv_dgrad (stride <= 2)
+    if (ds[i].stride < 1 || ds[i].stride > kMaxDgradStride) return -110;
   for (int i0 = 0; i0 < n; i0 += kXTBatch) {
     XTBatch b{};
     const int m = std::min(kXTBatch, n - i0);

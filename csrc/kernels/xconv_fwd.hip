@@ -14,6 +14,10 @@ int& xstage_mode() {
   static int mode = 1;
   return mode;
 }
+XLast& last_launch() {
+  static XLast l{};
+  return l;
+}
 }  // namespace xg
 
 namespace {
@@ -243,7 +247,7 @@ __global__ __launch_bounds__(256) void ximg_kernel(const XArgs a) {
         float v = acc[i][j][r];
         if (bias) v += bv;
         if (res) v += res[o];
-        if (a.relu) v = fmaxf(v, 0.f);
+        if (a.relu) v = relu_nan(v);
         vmax = fmaxf(vmax, fabsf(v));
         out[o] = v;
       }
@@ -413,7 +417,7 @@ __global__ __launch_bounds__(256) void ximg2_kernel(const XArgs a) {
         float v = acc[i][0][r];
         if (bias) v += bv;
         if (res) v += res[o];
-        if (a.relu) v = fmaxf(v, 0.f);
+        if (a.relu) v = relu_nan(v);
         vmax = fmaxf(vmax, fabsf(v));
         out[o] = v;
       }
@@ -430,6 +434,7 @@ int ximg_go(const XArgs& a, int G, hipStream_t st) {
   XArgs b = a;
   b.tiles_n = ceil_div(a.Ncol, BN);
   const dim3 grid((unsigned)(ceil_div(a.N, IMGS) * b.tiles_n), G, 1);
+  xg::last_launch() = XLast{3, W, BN, a.wp != nullptr, 0, 1, 1, 0};
   if (a.wp) hipLaunchKernelGGL((ximg_kernel<W, IMGS, BN, WM, WN, true>), grid, dim3(256), 0, st, b);
   else hipLaunchKernelGGL((ximg_kernel<W, IMGS, BN, WM, WN, false>), grid, dim3(256), 0, st, b);
   DBA_LAUNCH_CHECK();
@@ -452,6 +457,7 @@ int ximg2_go(const XArgs& a, int G, hipStream_t st) {
   XArgs b = a;
   b.tiles_n = ceil_div(a.Ncol, BN);
   const dim3 grid((unsigned)(ceil_div(a.N, IMGS) * b.tiles_n), G, 1);
+  xg::last_launch() = XLast{4, W, BN, 1, 0, 1, 1, 0};
   hipLaunchKernelGGL((ximg2_kernel<W, IMGS, BN>), grid, dim3(256), LDS, st, b);
   DBA_LAUNCH_CHECK();
 }
@@ -622,7 +628,7 @@ __global__ __launch_bounds__(256) void xstage16_kernel(const XArgs a) {
       const float4 rv = *(const float4*)(res + o + n);
       v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
     }
-    if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (a.relu) relu_nan4(v);
     vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
     *(float4*)(out + o + n) = v;
   }
@@ -647,6 +653,7 @@ int xstage16_try(const XArgs& a, int G, int KH, int KW, hipStream_t st) {
   if (a.bf.mode || a.lz_coef || a.sc_src) return -100;
   if (!aligned16(a.src) || !aligned16(a.w) || a.src_gstride % 4 || a.w_sstride % 4) return -100;
   if (!a.wp || !a.wf || ((uintptr_t)a.wf & 15) || a.wf_sstride % 8 || a.wf_sstride < 2 * 64 * 576) return -100;
+  xg::last_launch() = XLast{5, 16, 64, 1, 0, 1, 1, 0};
   hipLaunchKernelGGL(xstage16_kernel, dim3((unsigned)(a.N * (a.Ho / 8)), G, 1), dim3(256), 0, st, a);
   DBA_LAUNCH_CHECK();
 }
@@ -688,6 +695,14 @@ DBA_EXPORT int dba_xsplit_policy(int target, int min_k, int max_s, int kslab_max
   if (min_k > 0) p.min_k = min_k;
   if (max_s > 0) p.max_s = std::min(max_s, kSkMax);
   if (kslab_max > 0) p.kslab_max = kslab_max;
+  return 0;
+}
+
+// the last conv-family launch (common.hpp XLast) as 8 ints
+DBA_EXPORT int dba_xconv_last_launch(int* out) {
+  const XLast& l = xg::last_launch();
+  const int v[8] = {l.kind, l.tile, l.vec, l.pre, l.form, l.slabs, l.nclass, l.lazy};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   return 0;
 }
 

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void xhalo_kernel(const XArgs a) {
         const float4 sc = *(const float4*)&lzs[q * 4], sh = *(const float4*)&lzs[CS + q * 4];
         float4 v = pv[u];
         v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
-        if (a.lz_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (a.lz_relu) relu_nan4(v);
         if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
         split4h(v.x, v.y, v.z, v.w, hs.ma, sp);
       } else {
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void xhalo_kernel(const XArgs a) {
       const float4 rv = *(const float4*)(res + o + n);
       v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
     }
-    if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (a.relu) relu_nan4(v);
     if (a.bf.mode == 2) {   // backward: d = the gradient where the BN(+ReLU) output is > 0
       v = bnf_mask4(a.bf, g, o, n, v);
       *(float4*)&Ct[row * BN + cc] = v;
@@ -338,6 +338,7 @@ int xhalo_go(const XArgs& a, int G, hipStream_t st) {
   XArgs b = a;
   b.tiles_n = ceil_div(a.Ncol, BN);
   const dim3 grid((unsigned)(a.N * (a.Ho / (BM / W)) * b.tiles_n), G, 1);
+  xg::last_launch() = XLast{2, W, CS, PRE, 0, 1, 1, LZ};
   hipLaunchKernelGGL((xhalo_kernel<W, CS, BM, BN, WM, WN, PRE, LZ, SC>), grid, dim3(256), 0, st, b);
   DBA_LAUNCH_CHECK();
 }

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void xwgrad_kernel(const XWArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = fmaf(xv[st][r][e], xsc[e], xsh[e]);
-          if (a.x_relu) v = fmaxf(v, 0.f);
+          if (a.x_relu) v = relu_nan(v);
           xv[st][r][e] = ((s_xok[st] >> (r * 4 + e)) & 1u) ? v : 0.f;
         }
       }
@@ -289,7 +289,8 @@ __global__ __launch_bounds__(256) void xwgrad_reduce_kernel(const float* __restr
 }
 
 // the deferred weight-gradient reductions of a whole backward pass in one launch
-// (blockIdx.y = descriptor, blockIdx.z = replica): same fixed z order as xwgrad_reduce_kernel
+// (blockIdx.y = descriptor, blockIdx.z = replica): a fixed order of its own (xwr_body's z-groups),
+// which is xwgrad_reduce_kernel's serial z order only up to 4 slabs
 struct XWRDesc {   // all int64 (built from a torch int64 host tensor)
   long long ws, dw, dw_gstride, per, nvalid, N, HoWo, mchunk, G, unused;
 };
@@ -476,6 +477,7 @@ DBA_EXPORT int dba_xwgrad(const float* dy, long long dy_gstride, const float* x,
     XWHArgs h{dy, dy_gstride, x, x_gstride, ws, nvalid, N, H, amax_dy, amax_dy_ld, amax_x, amax_x_ld, x_coef, x_relu};
     const int rc = xwgrad_halo_launch(h, G, W, Cin, st);
     if (rc != -100) {
+      xg::last_launch() = XLast{8, W, 4, 0, 0, Z, 1, x_coef != nullptr};
       if (rc != 0 || defer) return rc;
       const long long per = (long long)Cout * a.K;
       const dim3 g2((unsigned)std::max(1LL, std::min(1024LL, (per + 255) / 256)), G);
@@ -493,6 +495,7 @@ DBA_EXPORT int dba_xwgrad(const float* dy, long long dy_gstride, const float* x,
   if (!amax_dy || !amax_x) return -109;   // the fp16 pair needs both operand maxima
   const int bno = Cout <= 32 ? 32 : Cout <= 64 ? 64 : 128;
   const dim3 grid((unsigned)(ceil_div(Cout, bno) * a.tiles_k), G, Z);
+  xg::last_launch() = XLast{7, bno, v4 ? 4 : 1, 0, M % mchunk != 0, Z, 1, x_coef != nullptr};
 #define XW_GO(BNO_, WN__, WK__, V_, X_) \
   hipLaunchKernelGGL((xwgrad_kernel<BNO_, 128, WN__, WK__, V_, X_>), grid, dim3(256), 0, st, a)
 #define XW_P(V_, X_)                                  \

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void xwgrad_halo_kernel(const XWHArgs a) {
         const bool ok = (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)W;
         v.x = fmaf(v.x, lsc.x, lsh.x); v.y = fmaf(v.y, lsc.y, lsh.y); v.z = fmaf(v.z, lsc.z, lsh.z);
         v.w = fmaf(v.w, lsc.w, lsh.w);
-        if (a.x_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (a.x_relu) relu_nan4(v);
         if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
       }
       uint2 sp[2];

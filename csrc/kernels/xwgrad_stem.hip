@@ -144,6 +144,7 @@ __global__ __launch_bounds__(256, 2) void xwgrad_stem_kernel(const XWSArgs a) {
 template <int W>
 int go(const XWSArgs& a, int G, hipStream_t st) {
   const int blocks = a.N * a.H * W / kPix;
+  xg::last_launch() = XLast{9, W, 1, 0, 0, blocks, 1, a.coef != nullptr};
   hipLaunchKernelGGL(xwgrad_stem_kernel<W>, dim3(blocks, G), dim3(256), 0, st, a);
   DBA_LAUNCH_CHECK();
 }

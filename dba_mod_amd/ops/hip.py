@@ -123,6 +123,7 @@ _SIGS = {
                       _P, _LL, _I, _P, _F, _F, _P, _P],
     "dba_xdown_fwd": [_P, _LL, _P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _P] + [_I] * 8
     + [_P, _I] * 5 + [_P],
+    "dba_xconv_last_launch": [_P],
     "dba_xstem_fwd": [_P, _LL, _P, _LL, _P, _P, _LL, _P, _P, _LL, _P] + [_I] * 13 + [_P, _I, _P, _P],
 }
 for _name, _args in _SIGS.items():
@@ -282,6 +283,16 @@ def _check_w(w: Tensor, dt: torch.dtype = _F32) -> Tuple[Tensor, int]:
         raise TypeError(f"conv weights: dtype {w.dtype} does not match the {dt} activations "
                         f"(no silent precision conversion)")
     return _rowview(w)
+
+
+def last_conv_launch() -> dict:
+    """The conv family's last main-kernel launch of this process (common.hpp ``XLast``): kernel kind,
+    tile, staging vector, pre-split planes, split-K form, slabs, parity classes, lazy operand.  The
+    tests check with it that a shape reached the kernel they name.  One unsynchronised record per
+    process: read it right after the call, on the calling thread, with no other thread launching convs."""
+    a = (ctypes.c_int * 8)()
+    _L.dba_xconv_last_launch(ctypes.cast(a, ctypes.c_void_p))
+    return dict(zip(("kind", "tile", "vec", "pre", "form", "slabs", "nclass", "lazy"), (int(v) for v in a)))
 
 
 def set_ximg(on: int) -> int:
@@ -742,11 +753,22 @@ def conv2d(x, w, wsel, stride, pad, bias=None, residual=None, relu=False, nvalid
     return _xconv_fwd(_act(x, _F32, "conv input"), w, wsel, stride, pad, bias, residual, relu, nvalid, out_dtype)
 
 
+MAX_DGRAD_STRIDE = 2   # xconv_dgrad.hip kMaxDgradStride: the parity-class tables hold s * s <= 4 entries
+
+
+def _check_dgrad_stride(stride: int) -> None:
+    if not 1 <= int(stride) <= MAX_DGRAD_STRIDE:
+        raise ValueError(f"conv data gradient: stride {stride} is not supported (1 .. {MAX_DGRAD_STRIDE}: the "
+                         f"kernel's parity-class table holds {MAX_DGRAD_STRIDE ** 2} classes)")
+
+
 def _xtranspose(items) -> list:
     """Parity-class packed fp32 data-gradient weights (xconv_dgrad.hip xtranspose_kernel) of
     ``items = [(w, stride, pad, nvalid_or_None)]`` (same slot count) in ONE launch."""
     outs, desc, max_per, nv = [], [], 0, None
     slots = items[0][0].shape[0]
+    for _, stride, _, _ in items:
+        _check_dgrad_stride(stride)
     for w, stride, pad, nvalid in items:
         wv, ws = _check_w(w, _F32)
         _, Cout, KH, KW, Cin = wv.shape
@@ -781,6 +803,7 @@ def prepare_dgrad_weights(ref, items):
 def _xconv_dgrad(dy, w, wsel, stride, pad, in_hw, nvalid, out_dtype, accum, wt, finish=None):
     if out_dtype not in (None, _F32):
         raise TypeError(f"fp32 dgrad cannot emit {out_dtype} (no silent precision conversion)")
+    _check_dgrad_stride(stride)
     G, N, Ho, Wo, Cout = dy.shape
     wv, _ = _check_w(w, _F32)
     slots, _, KH, KW, Cin = wv.shape
