@@ -1,5 +1,5 @@
 // Row helpers shared by the aggregation kernels over strided client rows (clip.hip, krum.hip,
-// trim.hip, rlr.hip): a lane takes four consecutive 4-byte elements of a row per step, as one
+// coordrank.hpp with its rules trim.hip and bulyan.hip, rlr.hip): a lane takes four consecutive 4-byte elements of a row per step, as one
 // 16-byte access where the row start is 16-byte aligned and as four scalar ones otherwise
 // (finals[:, :n_upd] is a strided view whose rows may start anywhere); the last, partial step
 // touches only the row's remaining elements.  Which elements a thread takes never depends on the

@@ -1,4 +1,4 @@
-// Compile-time sorting networks for register-resident keys (trim.hip).
+// Compile-time sorting networks for register-resident keys (coordrank.hpp: trim.hip, bulyan.hip).
 //   * kSortNet<N> is the comparator list of an N-input network: Batcher's odd-even merge sort on
 //     the next power of two P >= N with every comparator that touches an input >= N dropped.  The
 //     inputs N .. P - 1 would hold top-valued sentinels in the top positions; a comparator whose

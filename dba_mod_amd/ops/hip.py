@@ -1467,7 +1467,33 @@ def pairwise_sq_dists(buf, row_idx=None):
     return out
 
 
-TRIM_MAX_ROWS = 64         # trim.hip kMaxRows
+TRIM_MAX_ROWS = 64         # coordrank.hpp kMaxRows
+BULYAN_MAX_ROWS = 64       # the same pass
+
+
+def _coord_rank(op, ref, check, max_rows, buf, base, arg, row_idx):
+    """The coordinate-rank pass ``dba_coord_<op>`` (coordrank.hpp) over the picked rows of ``buf``:
+    (total fp64 [L], kept int64 [n], high int64 [n]).  ``check(n, arg)`` validates the rule's integer;
+    beyond ``max_rows`` rows or 2^31 coordinates the reference composition ``ref`` on the device."""
+    buf, rs, idx, n = _picked_rows(ref.__name__, buf, row_idx)
+    L = buf.shape[1]
+    assert base.dtype == torch.float32 and base.device == buf.device
+    assert base.numel() == L, (tuple(buf.shape), base.numel())
+    arg = check(n, arg)
+    if n > max_rows or L >= 1 << 31:
+        return ref(buf, base, arg, row_idx)
+    if n == 0 or L == 0:
+        return (torch.zeros(L, dtype=torch.float64, device=buf.device),
+                torch.zeros(n, dtype=torch.int64, device=buf.device),
+                torch.zeros(n, dtype=torch.int64, device=buf.device))
+    base = base.contiguous()
+    total = torch.empty(L, dtype=torch.float64, device=buf.device)
+    counts = torch.empty(n, 2, dtype=torch.int64, device=buf.device)
+    blocks = int(getattr(_L, f"dba_coord_{op}_blocks")(L))
+    part = torch.empty(2 * n * blocks, dtype=torch.int64, device=buf.device)
+    _call(f"dba_coord_{op}", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), arg, L, total.data_ptr(),
+          counts.data_ptr(), part.data_ptr(), _stream())
+    return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
 
 
 def trimmed_delta_sum(buf, base, k, row_idx=None):
@@ -1476,27 +1502,7 @@ def trimmed_delta_sum(buf, base, k, row_idx=None):
     numbers into ``buf``, repeats allowed), each coordinate sorted in registers, ranks k .. n - 1 - k
     added in ascending order in fp64; no atomics, bitwise run to run.  More than 64 rows (or 2^31
     coordinates) take the reference composition on the device."""
-    buf, rs, idx, n = _picked_rows("trimmed_delta_sum", buf, row_idx)
-    L = buf.shape[1]
-    assert base.dtype == torch.float32 and base.device == buf.device
-    assert base.numel() == L, (tuple(buf.shape), base.numel())
-    k = _ref.check_trim(n, k)
-    if n > TRIM_MAX_ROWS or L >= 1 << 31:
-        return _ref.trimmed_delta_sum(buf, base, k, row_idx)
-    if n == 0 or L == 0:
-        return (torch.zeros(L, dtype=torch.float64, device=buf.device),
-                torch.zeros(n, dtype=torch.int64, device=buf.device),
-                torch.zeros(n, dtype=torch.int64, device=buf.device))
-    base = base.contiguous()
-    total = torch.empty(L, dtype=torch.float64, device=buf.device)
-    counts = torch.empty(n, 2, dtype=torch.int64, device=buf.device)
-    part = torch.empty(2 * n * int(_L.dba_coord_trim_blocks(L)), dtype=torch.int64, device=buf.device)
-    _call("dba_coord_trim", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), k, L, total.data_ptr(),
-          counts.data_ptr(), part.data_ptr(), _stream())
-    return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
-
-
-BULYAN_MAX_ROWS = 64       # bulyan.hip kMaxRows
+    return _coord_rank("trim", _ref.trimmed_delta_sum, _ref.check_trim, TRIM_MAX_ROWS, buf, base, k, row_idx)
 
 
 def bulyan_delta_sum(buf, base, f, row_idx=None):
@@ -1505,24 +1511,7 @@ def bulyan_delta_sum(buf, base, f, row_idx=None):
     t row numbers into ``buf``, repeats allowed), each coordinate sorted in registers, the t - 2 f
     ranks closest to the lower median added in ascending order in fp64; no atomics, bitwise run to
     run.  More than 64 rows (or 2^31 coordinates) take the reference composition on the device."""
-    buf, rs, idx, t = _picked_rows("bulyan_delta_sum", buf, row_idx)
-    L = buf.shape[1]
-    assert base.dtype == torch.float32 and base.device == buf.device
-    assert base.numel() == L, (tuple(buf.shape), base.numel())
-    f = _ref.check_bulyan(t, f)
-    if t > BULYAN_MAX_ROWS or L >= 1 << 31:
-        return _ref.bulyan_delta_sum(buf, base, f, row_idx)
-    if t == 0 or L == 0:
-        return (torch.zeros(L, dtype=torch.float64, device=buf.device),
-                torch.zeros(t, dtype=torch.int64, device=buf.device),
-                torch.zeros(t, dtype=torch.int64, device=buf.device))
-    base = base.contiguous()
-    total = torch.empty(L, dtype=torch.float64, device=buf.device)
-    counts = torch.empty(t, 2, dtype=torch.int64, device=buf.device)
-    part = torch.empty(2 * t * int(_L.dba_coord_bulyan_blocks(L)), dtype=torch.int64, device=buf.device)
-    _call("dba_coord_bulyan", buf.data_ptr(), rs, _ptr(idx), t, base.data_ptr(), f, L, total.data_ptr(),
-          counts.data_ptr(), part.data_ptr(), _stream())
-    return total, counts[:, 0].contiguous(), counts[:, 1].contiguous()
+    return _coord_rank("bulyan", _ref.bulyan_delta_sum, _ref.check_bulyan, BULYAN_MAX_ROWS, buf, base, f, row_idx)
 
 
 RLR_MAX_ROWS = 65535       # rlr.hip kMaxGridY: the agreement pass takes one grid row per client

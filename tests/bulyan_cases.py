@@ -3,12 +3,11 @@ test_bulyan_aggregation.py, HIP kernel in test_gpu_bulyan.py): the generator of 
 one numpy fp64 oracle that does literally what the op is defined to do.  Every value is fixed by
 IEEE arithmetic in a stated order, so the tests compare bits: there is no tolerance."""
 import numpy as np
-import torch
 
 import trim_cases as tc
 
-# the launch grid of csrc/kernels/bulyan.hip: at most 512 blocks x 256 threads x 4 floats per step;
-# the GPU test sizes the wrap case from the kernel's own dba_coord_bulyan_blocks
+# the launch grid of the kernel is trim's (csrc/kernels/coordrank.hpp); the GPU test sizes the wrap
+# case from the kernel's own dba_coord_bulyan_blocks
 GRID_THREADS, GRID_QUAD = tc.GRID_THREADS, tc.GRID_QUAD
 
 # (t, L, rstride, column offset of the view, f): the smallest input; three rows down to their
@@ -20,6 +19,12 @@ SMALL_CASES = [(1, 1, 1, 0, 0), (3, 1, 1, 0, 1), (3, 5, 5, 0, 0), RECIPE_CASE, (
                (7, 1029, 1031, 2, 2), (9, 4099, 5000, 1, 3), (16, 130, 130, 0, 5), (17, 130, 131, 0, 8),
                (33, 70, 70, 0, 4), (64, 130, 130, 0, 31), (64, 130, 130, 0, 0)]
 NINE_ROWS = SMALL_CASES[6]
+# every instantiation of the kernel: each exact size at its largest f and at f = 0; either side of
+# each padded network size with an odd L (a partial step of the two-per-thread kernels), the sizes
+# themselves at their largest f, the next ones at a middle f
+SMALL_CASES += [tc.exact_case(t, (t - 1) // 2) for t in range(1, 17)]
+SMALL_CASES += [tc.exact_case(t, 0) for t in range(3, 17)]         # (one and two rows: 0 is the largest f)
+SMALL_CASES += [(t, 71, 71, 0, (t - 1) // 2 if t % 2 == 0 else t // 4) for t in (24, 25, 32, 33, 48, 49)]
 FALLBACK_CASE = (65, 33, 33, 0, 2)        # t > 64: the composition on the device
 
 case_id = tc.case_id
@@ -91,20 +96,5 @@ def greedy_window(col, f):
 
 
 def check(out, rows, base, f, tag=""):
-    """The op's (total, kept, high) against the oracle: dtypes and shapes, ``total`` equal (``==``,
-    which ignores the sign of a zero) wherever the oracle is not NaN and NaN exactly where it is,
-    the counts equal integers."""
-    total, kept, high = out
-    t, L = rows.shape
-    assert total.dtype == torch.float64 and tuple(total.shape) == (L,)
-    assert kept.dtype == torch.int64 and tuple(kept.shape) == (t,)
-    assert high.dtype == torch.int64 and tuple(high.shape) == (t,)
-    want_t, want_k, want_h = oracle(rows.numpy(), base.numpy(), f)
-    total, kept, high = total.cpu(), kept.cpu(), high.cpu()
-    want = torch.from_numpy(want_t)
-    nan = torch.isnan(want)
-    assert torch.equal(torch.isnan(total), nan), f"{tag}NaN positions differ"
-    bad = (total != want) & ~nan
-    assert torch.equal(total[~nan], want[~nan]), (tag, int(bad.sum()), total[bad][:4], want[bad][:4])
-    assert kept.tolist() == want_k.tolist(), (tag, kept.tolist(), want_k.tolist())
-    assert high.tolist() == want_h.tolist(), (tag, high.tolist(), want_h.tolist())
+    """The op's (total, kept, high) against the oracle, as trim_cases.check compares them."""
+    tc.check(out, rows, base, f, tag, oracle)

@@ -21,7 +21,7 @@ import trim_cases as tc
 from conftest import ROOT
 
 CFG = trim_cpu.CFG
-# one sweep of the launch grid of csrc/kernels/bulyan.hip (test_gpu_bulyan.py checks it against the kernel's own)
+# one sweep of the launch grid of csrc/kernels/coordrank.hpp (test_gpu_bulyan.py checks it against the kernel's own)
 SWEEP = 512 * bc.GRID_THREADS * bc.GRID_QUAD
 CASES = bc.SMALL_CASES + [bc.wrap_case(SWEEP), bc.FALLBACK_CASE]
 

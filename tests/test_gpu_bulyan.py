@@ -2,14 +2,13 @@
 oracle of bulyan_cases.py bit for bit (every case, a wrap of the launch grid, row_idx, non-finite
 values, degenerate shapes), the t > 64 composition, and one model-replacement round through
 ``Server``."""
-import functools
-
 import pytest
 import torch
 
 import bulyan_cases as bc
 import test_bulyan_aggregation as cpu
 import test_trim_aggregation as trim_cpu
+import trim_cases as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -21,36 +20,14 @@ def dev():
     return torch.device("cuda:0")
 
 
-@functools.lru_cache(maxsize=None)
-def _case(case):
-    return bc.make_case(*case)
-
-
-def _on_device(case, dev):
-    """The same strided view on the device (big[:, off:off + L] of a [t, rstride] buffer) and the base."""
-    t, L, rstride, off, _ = case
-    rows, base = _case(case)
-    big = torch.zeros(t, rstride, device=dev)
-    big[:, off:off + L] = rows.to(dev)
-    view = big[:, off:off + L]
-    assert view.stride(0) == rstride or t == 1
-    return view, base.to(dev)
-
-
-def _same(a, b):
-    """Two (total, kept, high) results with the same bits."""
-    return all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x,
-                           y.view(torch.int64) if y.dtype == torch.float64 else y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("case", bc.SMALL_CASES, ids=bc.case_id)
 def test_kernel_matches_oracle(dev, case):
     from dba_mod_amd import ops
-    view, base = _on_device(case, dev)
+    view, base = tc.on_device(case, dev)
     out = ops.bulyan_delta_sum(view, base, case[4])
     assert all(t.is_cuda for t in out)
-    bc.check(out, *_case(case), case[4])
-    assert _same(out, ops.bulyan_delta_sum(view, base, case[4]))            # bitwise run to run
+    bc.check(out, *tc.case_rows(case), case[4])
+    assert tc.same_bits(out, ops.bulyan_delta_sum(view, base, case[4]))     # bitwise run to run
 
 
 def test_wrap_case_wraps_the_grid(dev):
@@ -65,20 +42,20 @@ def test_wrap_case_wraps_the_grid(dev):
     assert H.BULYAN_MAX_ROWS == 64
     case = bc.wrap_case(sweep)
     assert int(H._L.dba_coord_bulyan_blocks(case[1])) == blocks
-    view, base = _on_device(case, dev)
-    bc.check(ops.bulyan_delta_sum(view, base, case[4]), *_case(case), case[4])
+    view, base = tc.on_device(case, dev)
+    bc.check(ops.bulyan_delta_sum(view, base, case[4]), *tc.case_rows(case), case[4])
 
 
 def test_row_idx_reads_rows_in_place(dev):
     """Rows taken out of order from a larger buffer, one index repeated: the bits of the gathered call."""
     from dba_mod_amd import ops
-    view, base = _on_device(bc.NINE_ROWS, dev)
+    view, base = tc.on_device(bc.NINE_ROWS, dev)
     idx = [7, 2, 5, 2, 8, 0, 3]
     out = ops.bulyan_delta_sum(view, base, 2, idx)
     assert tuple(out[1].shape) == (7,)
-    assert _same(out, ops.bulyan_delta_sum(view[idx].contiguous(), base, 2))
-    assert _same(out, ops.bulyan_delta_sum(view, base, 2, torch.tensor(idx, device=dev)))
-    rows, b = _case(bc.NINE_ROWS)
+    assert tc.same_bits(out, ops.bulyan_delta_sum(view[idx].contiguous(), base, 2))
+    assert tc.same_bits(out, ops.bulyan_delta_sum(view, base, 2, torch.tensor(idx, device=dev)))
+    rows, b = tc.case_rows(bc.NINE_ROWS)
     bc.check(out, rows[idx], b, 2)
     with pytest.raises(ValueError):
         ops.bulyan_delta_sum(view, base, 1, [0, 9, 1])
@@ -128,17 +105,17 @@ def test_degenerate_shapes_return_zeros(dev):
 
 def test_f0_is_the_plain_trimmed_sum(dev):
     from dba_mod_amd import ops
-    view, base = _on_device(bc.NINE_ROWS, dev)
-    assert _same(ops.bulyan_delta_sum(view, base, 0), ops.trimmed_delta_sum(view, base, 0))
+    view, base = tc.on_device(bc.NINE_ROWS, dev)
+    assert tc.same_bits(ops.bulyan_delta_sum(view, base, 0), ops.trimmed_delta_sum(view, base, 0))
 
 
 def test_more_than_64_rows_take_the_composition(dev):
     from dba_mod_amd import ops
     case = bc.FALLBACK_CASE
-    view, base = _on_device(case, dev)
+    view, base = tc.on_device(case, dev)
     out = ops.bulyan_delta_sum(view, base, case[4])
     assert all(t.is_cuda for t in out)
-    bc.check(out, *_case(case), case[4])
+    bc.check(out, *tc.case_rows(case), case[4])
 
 
 def test_server_round_drops_the_attacker(dev, tmp_path):

@@ -2,8 +2,6 @@
 the numpy oracle of trim_cases.py bit for bit (every case, a wrap of the launch grid, row_idx,
 non-finite values, degenerate shapes), the n > 64 composition, and one model-replacement round
 through ``Server``."""
-import functools
-
 import pytest
 import torch
 
@@ -20,36 +18,14 @@ def dev():
     return torch.device("cuda:0")
 
 
-@functools.lru_cache(maxsize=None)
-def _case(case):
-    return tc.make_case(*case)
-
-
-def _on_device(case, dev):
-    """The same strided view on the device (big[:, off:off + L] of a [n, rstride] buffer) and the base."""
-    n, L, rstride, off, _ = case
-    rows, base = _case(case)
-    big = torch.zeros(n, rstride, device=dev)
-    big[:, off:off + L] = rows.to(dev)
-    view = big[:, off:off + L]
-    assert view.stride(0) == rstride or n == 1
-    return view, base.to(dev)
-
-
-def _same(a, b):
-    """Two (total, kept, high) results with the same bits."""
-    return all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x,
-                           y.view(torch.int64) if y.dtype == torch.float64 else y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("case", tc.SMALL_CASES, ids=tc.case_id)
 def test_kernel_matches_oracle(dev, case):
     from dba_mod_amd import ops
-    view, base = _on_device(case, dev)
+    view, base = tc.on_device(case, dev)
     out = ops.trimmed_delta_sum(view, base, case[4])
     assert all(t.is_cuda for t in out)
-    tc.check(out, *_case(case), case[4])
-    assert _same(out, ops.trimmed_delta_sum(view, base, case[4]))           # bitwise run to run
+    tc.check(out, *tc.case_rows(case), case[4])
+    assert tc.same_bits(out, ops.trimmed_delta_sum(view, base, case[4]))    # bitwise run to run
 
 
 def test_wrap_case_wraps_the_grid(dev):
@@ -64,20 +40,20 @@ def test_wrap_case_wraps_the_grid(dev):
     assert H.TRIM_MAX_ROWS == 64
     case = tc.wrap_case(sweep)
     assert int(H._L.dba_coord_trim_blocks(case[1])) == blocks
-    view, base = _on_device(case, dev)
-    tc.check(ops.trimmed_delta_sum(view, base, case[4]), *_case(case), case[4])
+    view, base = tc.on_device(case, dev)
+    tc.check(ops.trimmed_delta_sum(view, base, case[4]), *tc.case_rows(case), case[4])
 
 
 def test_row_idx_reads_rows_in_place(dev):
     """Rows taken out of order from a larger buffer, one index repeated: the bits of the gathered call."""
     from dba_mod_amd import ops
-    view, base = _on_device(tc.NINE_ROWS, dev)
+    view, base = tc.on_device(tc.NINE_ROWS, dev)
     idx = [7, 2, 5, 2, 8, 0]
     out = ops.trimmed_delta_sum(view, base, 2, idx)
     assert tuple(out[1].shape) == (6,)
-    assert _same(out, ops.trimmed_delta_sum(view[idx].contiguous(), base, 2))
-    assert _same(out, ops.trimmed_delta_sum(view, base, 2, torch.tensor(idx, device=dev)))
-    rows, b = _case(tc.NINE_ROWS)
+    assert tc.same_bits(out, ops.trimmed_delta_sum(view[idx].contiguous(), base, 2))
+    assert tc.same_bits(out, ops.trimmed_delta_sum(view, base, 2, torch.tensor(idx, device=dev)))
+    rows, b = tc.case_rows(tc.NINE_ROWS)
     tc.check(out, rows[idx], b, 2)
     with pytest.raises(ValueError):
         ops.trimmed_delta_sum(view, base, 1, [0, 9, 1])
@@ -123,10 +99,10 @@ def test_degenerate_shapes_return_zeros(dev):
 def test_more_than_64_rows_take_the_composition(dev):
     from dba_mod_amd import ops
     case = tc.FALLBACK_CASE
-    view, base = _on_device(case, dev)
+    view, base = tc.on_device(case, dev)
     out = ops.trimmed_delta_sum(view, base, case[4])
     assert all(t.is_cuda for t in out)
-    tc.check(out, *_case(case), case[4])
+    tc.check(out, *tc.case_rows(case), case[4])
 
 
 def test_server_round_cuts_the_attacker(dev, tmp_path):

@@ -20,7 +20,7 @@ import trim_cases as tc
 from conftest import ROOT
 
 CFG = os.path.join(ROOT, "configs", "mnist_params.yaml")
-# one sweep of the launch grid of csrc/kernels/trim.hip (test_gpu_trim.py checks it against the kernel's own)
+# one sweep of the launch grid of csrc/kernels/coordrank.hpp (test_gpu_trim.py checks it against the kernel's own)
 SWEEP = 512 * tc.GRID_THREADS * tc.GRID_QUAD
 CASES = tc.SMALL_CASES + [tc.wrap_case(SWEEP), tc.FALLBACK_CASE]
 
