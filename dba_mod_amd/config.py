@@ -128,6 +128,16 @@ _DEFAULTS: Dict[str, Any] = {
     # median of the round's client update norms.  With diff_privacy the noise then sits on a sum
     # of bounded sensitivity
     "clip_norm": None,
+    # FLAME (with clip_norm: median only; Nguyen et al., USENIX Security 2022): the cosine distances
+    # between the clients' updates are clustered, the majority cluster (at least n // 2 + 1 clients,
+    # single linkage: what HDBSCAN returns with the paper's parameters) is admitted, the admitted
+    # updates are clipped to the round's median update norm S and averaged, and N(0, (lambda S)^2)
+    # noise is added.  clip_flame: None / false = off (plain clipping); true = FLAME (needs
+    # no_models >= 3; not with diff_privacy: FLAME sets its own noise level).  clip_flame_lambda
+    # (with clip_flame: true only): None = 0.001, the paper's value for image models; a finite
+    # float >= 0 = lambda (0 adds no noise)
+    "clip_flame": None,
+    "clip_flame_lambda": None,
     # Multi-Krum (aggregation "mean" only; Blanchard et al., NeurIPS 2017): each client is scored
     # by the sum of its n - f - 2 smallest squared distances to the other clients' final states and
     # the m best-scored clients are averaged.  krum_f: None = off; an integer >= 0 = f, the number
@@ -213,6 +223,16 @@ class Params(dict):
                     opt.sizes(self, int(self["no_models"]), "no_models")
             earlier.append(opt.key)
             earlier_on = earlier_on or on
+        if self.clip_flame:
+            if self.clip_norm != CLIP_MEDIAN:
+                raise ValueError(f"clip_flame needs clip_norm: {CLIP_MEDIAN!r} (got {self.clip_norm!r}): FLAME clips "
+                                 "to the round's median update norm")
+            if self["diff_privacy"]:
+                raise ValueError("clip_flame cannot be combined with diff_privacy (FLAME sets its own noise "
+                                 "level, clip_flame_lambda times the median update norm)")
+            check_flame_sizes(int(self["no_models"]), "no_models")
+        elif self.clip_flame_lambda is not None:
+            raise ValueError("clip_flame_lambda is set without clip_flame: true")
         if self.sparse_topk is not None and self["diff_privacy"]:
             raise ValueError("sparse_topk cannot be combined with diff_privacy (noise on the dropped "
                              "coordinates undoes the sparsity, noise on the kept ones publishes the support)")
@@ -225,6 +245,22 @@ class Params(dict):
     def clip_norm(self) -> Any:
         """The checked ``clip_norm``: None (off), the bound C as a float, or ``"median"``."""
         return check_clip_norm(self.get("clip_norm"))
+
+    @property
+    def clip_flame(self) -> Optional[bool]:
+        """The checked ``clip_flame``: None (plain clipping; ``false`` reads as None) or True (FLAME)."""
+        return check_clip_flame(self.get("clip_flame"))
+
+    @property
+    def clip_flame_lambda(self) -> Optional[float]:
+        """The checked ``clip_flame_lambda``: None (the default, ``FLAME_LAMBDA``) or lambda >= 0."""
+        return check_flame_lambda(self.get("clip_flame_lambda"))
+
+    @property
+    def flame_lambda(self) -> float:
+        """FLAME's noise factor lambda: ``clip_flame_lambda``, or ``FLAME_LAMBDA`` when it is None."""
+        v = self.clip_flame_lambda
+        return FLAME_LAMBDA if v is None else v
 
     @property
     def krum_f(self) -> Optional[int]:
@@ -320,6 +356,35 @@ def check_clip_norm(v: Any, key: str = "clip_norm") -> Any:
     if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
         return float(v)
     raise ValueError(f"{key} {v!r}: expected None, a finite number > 0 or {CLIP_MEDIAN!r}")
+
+
+FLAME_LAMBDA = 0.001     # the paper's noise factor for image models (sigma = lambda * median norm)
+
+
+def check_clip_flame(v: Any) -> Optional[bool]:
+    """None for None / False (plain clipping), True for True (FLAME); anything else is an error."""
+    if v is None or v is False:
+        return None
+    if v is True:
+        return True
+    raise ValueError(f"clip_flame {v!r}: expected None, false or true")
+
+
+def check_flame_lambda(v: Any) -> Optional[float]:
+    """None or a finite number >= 0 (returned as float; a bool, a string or a list is an error)."""
+    if v is None:
+        return None
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v >= 0:
+        return float(v)
+    raise ValueError(f"clip_flame_lambda {v!r}: expected None or a finite number >= 0")
+
+
+def check_flame_sizes(n: int, what: str = "n") -> int:
+    """FLAME's inequality for n clients: n >= 3 (with two clients the majority m = n // 2 + 1 is
+    both of them and nothing can be filtered).  Returns m."""
+    if n < 3:
+        raise ValueError(f"clip_flame needs {what} >= 3 (got {n})")
+    return n // 2 + 1
 
 
 def check_krum_int(key: str, v: Any, lo: int) -> Optional[int]:
@@ -429,7 +494,7 @@ class MeanOption(NamedTuple):
 
 # in the order ``Server._aggregate`` looks for them; at most one is set
 MEAN_OPTIONS = (
-    MeanOption("clip_norm", (), False, None),
+    MeanOption("clip_norm", ("clip_flame", "clip_flame_lambda"), False, None),
     MeanOption("krum_f", ("krum_m", "krum_bulyan"), True, krum_option_sizes),
     MeanOption("trim_k", (), True, lambda p, n, what: check_trim_sizes(n, p.trim_k, what)),
     MeanOption("rlr_threshold", (), False, lambda p, n, what: check_rlr_sizes(n, p.rlr_threshold, what)),

@@ -5,7 +5,7 @@ round's n client rows live is an argument: the rules whose sums decompose over c
 ``clip_norm``, ``rlr_threshold``, distributed RFA) take this rank's rows ``finals [len(idx), S]`` and
 a :class:`Shard` (the positions ``idx`` of those rows among the n, a sum and a max over the ranks;
 default: every row here, identity reductions); the rules that read every row (``krum_f``,
-``krum_bulyan``, ``trim_k``) take the server's gathered snapshot bank and the clients' slots ``row_idx`` and read
+``krum_bulyan``, ``trim_k``, ``clip_flame``) take the server's gathered snapshot bank and the clients' slots ``row_idx`` and read
 the rows in place.  Every rank applies the identical update redundantly, so no broadcast is
 needed and every rank ends the round with a bit-identical global model.  A rule returns what the
 server records: the two ``weight_result.csv`` columns (and what its log line needs).
@@ -22,6 +22,16 @@ server records: the two ``weight_result.csv`` columns (and what its log line nee
   fused HIP passes over the strided client rows (``ops.delta_stats``,
   ``ops.clipped_delta_sum_fixed``); the products ``s_i delta_i`` are not exactly summable in
   fp64, so the sum goes through the same fixed-point limbs as RFA / FoolsGold.
+* :func:`fedavg_flame` / :func:`flame_distances` / :func:`flame_admit` — FLAME (config ``clip_norm:
+  median`` with ``clip_flame``; Nguyen et al., USENIX Security 2022; not in the reference): the
+  clients are filtered by the direction of their updates, then clipped and noised.  The fp64 Gram
+  matrix of the n updates comes from one fused HIP pass over the final states where they lie
+  (``ops.delta_gram``: exact deltas, one fma per product, no atomics, a pair's bits independent of
+  the other rows); the cosine distances and the clustering are host fp64 arithmetic (single
+  linkage up to the first component of n // 2 + 1 clients: the closed form of HDBSCAN with the
+  paper's parameters); the admitted updates are clipped to the lower-median norm S with
+  :func:`clip_factors`, summed through :func:`clipped_part` and noised with sigma = lambda S.
+  Like Krum it reads every row on every rank and reduces nothing.
 * :func:`fedavg_krum` / :func:`krum_scores` / :func:`krum_select` — Multi-Krum (config ``krum_f``,
   ``krum_m``; Blanchard et al., NeurIPS 2017; not in the reference): the clients farthest from the
   crowd are dropped and the rest averaged.  The [n, n] squared distances between the final states
@@ -262,6 +272,113 @@ def clipped_total(rows: torch.Tensor, base: torch.Tensor, factors: torch.Tensor,
     part = clipped_part(rows, base, factors[idx].to(dev), E) if idx else wsum_zero(L, E, dev)
     total = where.reduce(part)
     return total if E is None else fixed_decode(total, E)
+
+
+def flame_distances(G: torch.Tensor) -> torch.Tensor:
+    """FLAME's cosine distances (fp64 [n, n], on the host) from the Gram matrix of the clients'
+    updates: ``c = G[i][j] / sqrt(G[i][i] * G[j][j])`` clamped to [-1, 1], ``D[i][j] = 1 - c``,
+    ``D[i][i] = 0``.  A client with ``G[i][i] == 0`` (it returned the global model) is at distance 1
+    from every other client (FoolsGold's zero-row convention).  A client whose ``G[i][i]`` is not
+    finite is unusable: its row and column, the diagonal included, are NaN, which is how
+    :func:`flame_admit` knows it.  A cosine between two usable clients that is not finite (the
+    product of two finite squared norms overflowed) says nothing about the angle and reads as
+    distance 1.  Host fp64 arithmetic in this order on a matrix every rank holds with the same
+    bits: every rank computes the same distances."""
+    g = G.detach().double().cpu().tolist()
+    n = len(g)
+    D = [[0.0] * n for _ in range(n)]
+    usable = [math.isfinite(g[i][i]) for i in range(n)]
+    for i in range(n):
+        for j in range(i, n):
+            if not (usable[i] and usable[j]):
+                d = math.nan
+            elif i == j:
+                d = 0.0
+            elif g[i][i] == 0.0 or g[j][j] == 0.0:
+                d = 1.0
+            else:
+                den = math.sqrt(g[i][i] * g[j][j])
+                c = g[i][j] / den if den > 0.0 else math.nan
+                d = 1.0 - min(1.0, max(-1.0, c)) if math.isfinite(c) else 1.0
+            D[i][j] = D[j][i] = d
+    return torch.tensor(D, dtype=torch.float64).reshape(n, n)
+
+
+def flame_admit(D: torch.Tensor) -> List[int]:
+    """FLAME's admitted clients (sorted) from the [n, n] cosine distances of
+    :func:`flame_distances`: with m = n // 2 + 1, the unordered pairs of usable clients (finite
+    ``D[i][i]``) are sorted by ``(D[i][j], i, j)`` and merged in that order (single linkage,
+    Kruskal); the first component to reach m members is admitted, whole (so at least m clients).
+    This is what HDBSCAN returns with the paper's ``min_cluster_size = n // 2 + 1``,
+    ``min_samples = 1``, ``allow_single_cluster = True``: no split of the hierarchy can leave two
+    clusters of more than half the clients, and mutual reachability with one sample is the plain
+    distance.  Fewer than m usable clients is an error.  Host arithmetic on a matrix every rank
+    holds with the same bits."""
+    d = D.detach().double().cpu().tolist()
+    n = len(d)
+    m = n // 2 + 1
+    usable = [i for i in range(n) if math.isfinite(d[i][i])]
+    if len(usable) < m:
+        raise RuntimeError(f"flame: only {len(usable)} of {n} clients have a finite update, fewer than the majority "
+                           f"m = n // 2 + 1 = {m}")
+    if m <= 1:
+        return usable[:1]
+    parent = list(range(n))
+    size = [1] * n
+
+    def find(i: int) -> int:
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    pairs = sorted((d[i][j], i, j) for a, i in enumerate(usable) for j in usable[a + 1:])
+    for _, i, j in pairs:
+        ri, rj = find(i), find(j)
+        if ri == rj:
+            continue
+        parent[rj] = ri
+        size[ri] += size[rj]
+        if size[ri] >= m:
+            return [k for k in usable if find(k) == ri]
+    raise RuntimeError(f"flame: no component of {m} clients among {len(usable)} usable ones (a distance is not "
+                       "comparable)")
+
+
+def fedavg_flame(global_state: torch.Tensor, finals: torch.Tensor, lam: float, eta: float, seed: int,
+                 n_update: int, row_idx: Optional[Sequence[int]] = None
+                 ) -> Tuple[List[float], List[float], List[int]]:
+    """In-place FLAME of the n clients' final states: the rows ``row_idx`` of ``finals`` (the
+    server's gathered snapshot bank, read in place) or all of ``finals`` [n, S]; n >= 3.  The Gram
+    matrix of the updates over the ``n_update`` leading entries (exactly the entries aggregated;
+    ``ops.delta_gram``: one fused HIP pass), :func:`flame_distances`, :func:`flame_admit` (the
+    admitted set A, L = |A|); S = the lower median of all n update norms sqrt(G[i][i]) (a
+    non-finite norm ranks as +inf) and the factors of :func:`clip_factors` against it; then ``w +=
+    (eta / L) * sum_{i in A} gamma_i delta_i`` over the admitted rows (the only ones gathered) in
+    client order, through the fixed-point limbs of :func:`clipped_part` (their grid from the
+    largest admitted norm, which bounds every |delta|), and N(0, (lam S)^2) noise per entry
+    (``lam`` = 0: none).  Every rank holds every row and computes the same bits redundantly: no
+    reduction.  Returns (factor applied [n]: gamma_i, 0.0 for a client not admitted; update norms
+    [n]; the admitted clients, sorted)."""
+    n = finals.shape[0] if row_idx is None else len(row_idx)
+    C.check_flame_sizes(n, "the round's clients")
+    base = global_state[:n_update]
+    G = ops.delta_gram(finals[:, :n_update], base, row_idx)
+    admitted = flame_admit(flame_distances(G))
+    sq = torch.diagonal(G).detach().double().cpu()
+    sq = torch.where(torch.isfinite(sq), sq, torch.full_like(sq, math.inf))
+    gamma, S = clip_factors(sq, C.CLIP_MEDIAN)
+    norms = sq.sqrt()
+    rows = finals[admitted if row_idx is None else [row_idx[i] for i in admitted]][:, :n_update]
+    E = fixed_exponent(float(norms[admitted].max()), len(admitted))
+    part = clipped_part(rows, base, gamma[admitted].to(base.device), E)
+    total = part if E is None else fixed_decode(part, E)
+    sigma = float(lam) * S
+    ops.add_noise_scaled(base, total, eta / len(admitted), sigma, seed, sigma > 0.0)
+    factors = [0.0] * n
+    for i in admitted:
+        factors[i] = float(gamma[i])
+    return factors, [float(x) for x in norms], admitted
 
 
 def krum_scores(D: torch.Tensor, f: int) -> torch.Tensor:

@@ -543,7 +543,7 @@ class Server:
         Client snapshots stay on their owner rank.  Only the rows some other rank reads are
         broadcast from their owners: the snapshots of clients whose tests are image-sharded across ranks
         (the round's longest clients, or every client without early local tests) and, for
-        RFA in gather mode, for Multi-Krum, Bulyan and the trimmed mean, the final states.  Aggregation itself reduces
+        RFA in gather mode, for Multi-Krum, Bulyan, the trimmed mean and FLAME, the final states.  Aggregation itself reduces
         (``_aggregate``)."""
         S, P = self.spec.S, self.spec.P
         world, rank = self.d.world, self.d.rank
@@ -569,9 +569,10 @@ class Server:
                               if j not in done_early and plan.jobs[j].model != 0)
             option = C.mean_option(self.params)
             if ((self.params["aggregation_methods"] == C.AGGR_GEO_MED and self._rfa_gather(len(plan.clients)))
-                    or (option is not None and option.gathers)):
+                    or (option is not None and (option.gathers or self.params.clip_flame))):
                 # (Multi-Krum scores every client against every other, the trimmed mean sorts every
-                # coordinate over all clients: every rank needs every final row)
+                # coordinate over all clients, FLAME takes the angle between every two updates: every
+                # rank needs every final row)
                 shared.update(c.final_snap for c in plan.clients)
             for s, t in local_snaps.items():
                 bank[s] = t
@@ -652,14 +653,24 @@ class Server:
         option = C.mean_option(p) if method == C.AGGR_MEAN else None
         key = option.key if option is not None else None
         # the rule's inequalities against the round's actual client count: Krum's m (Bulyan's theta), the trim
-        # count k, theta
+        # count k, theta, FLAME's majority m
         size = option.sizes(p, n, "the round's clients") if option is not None and option.sizes else None
+        if key == "clip_norm" and p.clip_flame:
+            size = C.check_flame_sizes(n, "the round's clients")
         cols: Optional[Tuple[List[float], List[float]]] = None      # the two weight_result.csv columns
 
         def starred(shares: List[float]) -> str:
             return ", ".join(f"{nm}{'*' if p.is_adversary(nm) else ''}: {v:.4f}" for nm, v in zip(names, shares))
 
-        if key == "clip_norm":
+        if key == "clip_norm" and p.clip_flame:
+            lam = p.flame_lambda
+            *cols, admitted = agg.fedavg_flame(g, bank, lam, eta, dp_seed, n_upd, row_idx=slots)
+            chosen = [names[i] for i in admitted]
+            bound = agg.clip_bound(cols[1], p.clip_norm)
+            log.info(f"[flame agg] n: {n}  m: {size}  admitted: {chosen}  "
+                     f"adversaries admitted: {sum(1 for nm in chosen if p.is_adversary(nm))}/{len(chosen)}  "
+                     f"S: {bound}  sigma: {lam * bound}  factors (* adversary): {starred(cols[0])}")
+        elif key == "clip_norm":
             cols = agg.fedavg_clipped(g, finals, p.clip_norm, eta, no_models, *tail, where)
             bound = agg.clip_bound(cols[1], p.clip_norm)
             log.info(f"[clip agg] C: {bound}  clipped: {sum(v > bound for v in cols[1])}/{n}  factors: {cols[0]}")

@@ -69,6 +69,9 @@ _SIGS = {
     # Multi-Krum pairwise distances (csrc/kernels/krum.hip)
     "dba_pairwise_sqdist_blocks": [_LL],
     "dba_pairwise_sqdist": [_P, _LL, _P, _I, _LL, _P, _P, _P],
+    # FLAME's Gram matrix of the client updates (csrc/kernels/dgram.hip)
+    "dba_delta_gram_blocks": [_LL],
+    "dba_delta_gram": [_P, _LL, _P, _I, _P, _LL, _P, _P, _P],
     # coordinate-wise trimmed mean / median (csrc/kernels/trim.hip)
     "dba_coord_trim_blocks": [_LL],
     "dba_coord_trim": [_P, _LL, _P, _I, _P, _I, _LL, _P, _P, _P, _P],
@@ -1464,6 +1467,33 @@ def pairwise_sq_dists(buf, row_idx=None):
     nb = int(_L.dba_pairwise_sqdist_blocks(L))
     part = torch.empty(n * (n - 1) // 2 * nb, dtype=torch.float64, device=buf.device)
     _call("dba_pairwise_sqdist", buf.data_ptr(), rs, _ptr(idx), n, L, out.data_ptr(), part.data_ptr(), _stream())
+    return out
+
+
+GRAM_MAX_ROWS = 64         # dgram.hip kMaxRows
+
+
+def delta_gram(buf, base, row_idx=None):
+    """fp64 [n, n] Gram matrix of the updates ``buf[row] - base`` (dgram.hip): the rows are read where
+    they lie (``row_idx``: n row numbers into ``buf`` [R, L], repeats allowed) against ``base`` [L],
+    the deltas formed exactly in fp64, every unordered pair i <= j accumulated once with one fma per
+    product and mirrored; no atomics, bitwise run to run, and a pair's bits do not depend on the
+    rows' alignment or on the other rows of the call.  More than 64 rows take the reference
+    composition on the device."""
+    buf, rs, idx, n = _picked_rows("delta_gram", buf, row_idx)
+    L = buf.shape[1]
+    assert base.dtype == torch.float32 and base.device == buf.device
+    assert base.numel() == L, (tuple(buf.shape), base.numel())
+    if n > GRAM_MAX_ROWS:
+        return _ref.delta_gram(buf, base, row_idx)
+    if n == 0 or L == 0:
+        return torch.zeros(n, n, dtype=torch.float64, device=buf.device)
+    base = base.contiguous()
+    out = torch.empty(n, n, dtype=torch.float64, device=buf.device)
+    nb = int(_L.dba_delta_gram_blocks(L))
+    part = torch.empty(n * (n + 1) // 2 * nb, dtype=torch.float64, device=buf.device)
+    _call("dba_delta_gram", buf.data_ptr(), rs, _ptr(idx), n, base.data_ptr(), L, out.data_ptr(), part.data_ptr(),
+          _stream())
     return out
 
 

@@ -219,5 +219,14 @@ def _gram(feats: Tensor) -> Tensor:
 gram = _both("gram", lambda f: _ref.gram(f), lambda f: _hip().gram(f), _gram)
 
 
+def _delta_gram(buf: Tensor, base: Tensor, row_idx: Optional[List[int]]) -> Tensor:
+    """fp64 Gram matrix of the updates buf[row] - base over the picked rows (FLAME's cosine stage)."""
+    return _impl("delta_gram", buf)(buf, base, row_idx)
+
+
+delta_gram = _both("delta_gram", lambda x, b, idx: _ref.delta_gram(x, b, idx),
+                   lambda x, b, idx: _hip().delta_gram(x, b, idx), _delta_gram)
+
+
 OPS: List[str] = ["conv2d", "conv2d_dgrad", "conv2d_wgrad", "conv_bn_stats", "bn_apply", "gather_images",
-                  "softmax_xent", "sgd_step", "delta_sum", "sq_dists", "weighted_sum", "gram"]
+                  "softmax_xent", "sgd_step", "delta_sum", "sq_dists", "weighted_sum", "gram", "delta_gram"]

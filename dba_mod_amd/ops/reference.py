@@ -640,6 +640,28 @@ def pairwise_sq_dists(buf: Tensor, row_idx=None) -> Tensor:
     return D + D.t()
 
 
+def delta_gram(buf: Tensor, base: Tensor, row_idx=None) -> Tensor:
+    """fp64 [n, n] Gram matrix of the client updates (FLAME's cosine stage; dgram.hip is the GPU
+    form): ``G[i][j] = sum_k d_i[k] d_j[k]`` with ``d_i = (double)buf[row_i] - (double)base`` (exact
+    for fp32 operands), rows ``row_idx`` (n row numbers, repeats allowed) or all of ``buf`` [R, L]
+    fp32, ``base`` [L] fp32.  Pair by pair and chunked over L, so no [n, n, L] temporary; each
+    unordered pair i <= j is summed once, the diagonal by the same expression, and mirrored:
+    bitwise symmetric, and a pair's bits do not depend on the other rows of the call.  A NaN / Inf
+    element makes its row's entries non-finite and leaves the others alone."""
+    idx, n = _picked_rows(buf, row_idx)
+    L = buf.shape[1]
+    assert base.numel() == L, (tuple(buf.shape), base.numel())
+    G = torch.zeros(n, n, dtype=torch.float64, device=buf.device)
+    b = base.reshape(-1).double()
+    for c0 in range(0, L, PAIRWISE_CHUNK):
+        x = buf[:, c0:c0 + PAIRWISE_CHUNK]
+        d = (x if idx is None else x.index_select(0, idx)).double() - b[None, c0:c0 + PAIRWISE_CHUNK]
+        for i in range(n):
+            for j in range(i, n):
+                G[i, j] += (d[i] * d[j]).sum()
+    return torch.triu(G) + torch.triu(G, 1).t()
+
+
 TRIM_CHUNK = 1 << 18
 
 

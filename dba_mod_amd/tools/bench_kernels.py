@@ -395,6 +395,63 @@ def _bench_bulyan(name, t, S, f, reps, dev, rounds=5):
     return out
 
 
+# FLAME's Gram matrix of the updates (dgram.hip): a CIFAR round's 10 final states against the global model
+FLAME = [("flame.cifar", 10, 2_802_430)]
+
+
+def _bench_flame(name, n, S, reps, dev, rounds=5):
+    """The fused Gram kernel over n final-state rows read where they lie in a 21-row snapshot bank
+    (every other row), against (a) ``pairwise_sq_dists`` over the same rows — Multi-Krum's pass: n
+    rows where the Gram reads n + 1, 45 subtractions and 45 fma per coordinate where the Gram does
+    55 fma: the yardstick is its time x (n + 1) / n — and (b) ``delta_sum`` over the same rows, the
+    byte floor.  The three are timed in turn, ``rounds`` times over, in this process: the median
+    of each and its min .. max (the spread a difference has to leave to mean anything).  GB/s counts
+    (n + 1) * S * 4 bytes for the Gram and n * S * 4 for the others.  Before anything is timed the
+    kernel is checked against the reference op on the device: G within the tests' bound (L + 2)
+    2^-52 A, the same admitted set, the same median client and its norm S within (L + 4) 2^-53."""
+    from dba_mod_amd.fl import aggregate as agg
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    base = torch.randn(S, device=dev)
+    common = torch.randn(S, device=dev)
+    bank = base[None] + 0.01 * (common[None] + torch.randn(21, S, device=dev))   # finals in the odd slots
+    bank[3] = base + 100.0 * (bank[3] - base)                             # a model-replacement client
+    bank[7] = base + 0.01 * torch.randn(S, device=dev)                    # one with a direction of its own
+    slots = torch.arange(1, 2 * n + 1, 2, device=dev)
+    rows = bank[1:2 * n + 1:2]                                            # the same rows as a strided view
+    assert rows.shape[0] == n and torch.equal(rows, bank[slots])
+    G = H.delta_gram(rows, base)
+    assert torch.equal(G, H.delta_gram(bank, base, slots)) and torch.equal(G, G.t())
+    Gr = R.delta_gram(bank, base, slots)
+    d = (rows.double() - base.double()[None]).abs()
+    A = d @ d.t()
+    del d
+    assert bool(((G - Gr).abs() <= (S + 2) * 2.0 ** -52 * A).all())
+    admitted = agg.flame_admit(agg.flame_distances(G))
+    assert admitted == agg.flame_admit(agg.flame_distances(Gr))
+    e, er = torch.diagonal(G).cpu().sqrt(), torch.diagonal(Gr).cpu().sqrt()
+    med = int(torch.sort(e).indices[(n - 1) // 2])
+    assert med == int(torch.sort(er).indices[(n - 1) // 2])
+    bound, bound_r = agg.clip_bound(e, "median"), agg.clip_bound(er, "median")
+    assert abs(bound - bound_r) <= (S + 4) * 2.0 ** -53 * bound_r
+    fns = {"gram": lambda: H.delta_gram(rows, base), "krum": lambda: H.pairwise_sq_dists(rows),
+           "delta_sum": lambda: H.delta_sum(rows, base)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(_time(fn, reps))
+    out = {"shape": name, "n": n, "S": S, "rounds": rounds, "admitted": admitted, "median_norm": bound}
+    for k, v in times.items():
+        v = sorted(v)
+        med_t = v[len(v) // 2]
+        b = (n + 1 if k == "gram" else n) * S * 4
+        out.update({f"{k}_us": round(med_t * 1e6, 1), f"{k}_min_us": round(v[0] * 1e6, 1),
+                    f"{k}_max_us": round(v[-1] * 1e6, 1), f"{k}_GBps": round(b / med_t / 1e9, 1)})
+    out["gram_vs_krum"] = round(out["gram_us"] / out["krum_us"], 3)
+    out["yardstick"] = round((n + 1) / n, 3)
+    return out
+
+
 # robust learning rate (rlr.hip): a CIFAR round's 10 final states, theta = 4 as in configs/cifar_rlr.yaml
 RLR = [("rlr.cifar", 10, 2_802_430, 4)]
 
@@ -544,6 +601,10 @@ def main(argv=None) -> int:
     for name, t, S, f in BULYAN:
         if args.only in name:
             rows.append(_bench_bulyan(name, t, S, f, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, n, S in FLAME:
+        if args.only in name:
+            rows.append(_bench_flame(name, n, S, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     for name, n, S, theta in RLR:
         if args.only in name:
