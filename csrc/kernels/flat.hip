@@ -181,7 +181,118 @@ __global__ void distgrad_kernel(const float* __restrict__ w, long long ws, const
     gg[k] = fmaf(alpha, gg[k], c * (wg[k] - bg[k]));
 }
 
+// How the blocks of one replica row walk its n entries: entries [h, h + 4 nv) as nv float4 (both
+// row pointers 16-byte aligned from entry h on), the other h + (n - h - 4 nv) <= 6 entries one
+// by one.  Rows whose two pointers are misaligned differently have nv = 0 (all entries one by
+// one).  Nothing at or past n is touched.
+struct BallSpan {
+  long long h, nv;
+  __device__ BallSpan(const float* wg, const float* bg, long long n) {
+    const unsigned mw = ((unsigned)(uintptr_t)wg & 15u) >> 2, mb = ((unsigned)(uintptr_t)bg & 15u) >> 2;
+    if (mw != mb) {
+      h = 0;
+      nv = 0;
+    } else {
+      h = std::min<long long>((4 - mw) & 3, n);
+      nv = (n - h) >> 2;
+    }
+  }
+  // the k-th entry outside the float4 body, k in [0, n - 4 nv)
+  __device__ long long edge(long long k) const { return k < h ? k : k + 4 * nv; }
+};
+
+// PGD attacker, launch 1: part[g][blk] = this block's fp64 sum of (w_g - base_g)^2 over the first
+// n entries (replicas training with a trigger only).  The difference of two floats is exact in
+// fp64; one fma per entry, then a wave and a block reduction in a fixed order
+__global__ __launch_bounds__(256) void ballnorm_kernel(const float* __restrict__ w, long long ws,
+                                                       const float* __restrict__ base, long long bs,
+                                                       const int* __restrict__ trig, const int* __restrict__ active,
+                                                       long long n, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int g = blockIdx.y;
+  if (trig[g] < 0 || active[g] == 0) return;
+  const float* wg = w + (long long)g * ws;
+  const float* bg = base + (long long)g * bs;
+  const BallSpan sp(wg, bg, n);
+  const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x, dt = (long long)gridDim.x * blockDim.x;
+  double s = 0.0;
+  for (long long i = t0; i < sp.nv; i += dt) {
+    const float4 a = *reinterpret_cast<const float4*>(wg + sp.h + 4 * i);
+    const float4 b = *reinterpret_cast<const float4*>(bg + sp.h + 4 * i);
+    const double d0 = (double)a.x - (double)b.x, d1 = (double)a.y - (double)b.y;
+    const double d2 = (double)a.z - (double)b.z, d3 = (double)a.w - (double)b.w;
+    s = fma(d0, d0, s);
+    s = fma(d1, d1, s);
+    s = fma(d2, d2, s);
+    s = fma(d3, d3, s);
+  }
+  for (long long k = t0; k < n - 4 * sp.nv; k += dt) {
+    const long long e = sp.edge(k);
+    const double d = (double)wg[e] - (double)bg[e];
+    s = fma(d, d, s);
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) part[(long long)g * gridDim.x + blockIdx.x] = s;
+}
+
+__device__ __forceinline__ float ball_pull(float w, float b, double s) {
+  return (float)__dadd_rn((double)b, __dmul_rn(s, (double)w - (double)b));
+}
+
+// launch 2: norm = sqrt(sum of the replica's parts, in block order); a finite norm > radius pulls
+// w_g onto the sphere, w = base + (radius / norm)(w - base) in fp64 rounded once, anything else
+// writes nothing to w.  Thread (0, g) publishes the norm and counts the projection
+__global__ __launch_bounds__(256) void ballproj_kernel(float* __restrict__ w, long long ws,
+                                                       const float* __restrict__ base, long long bs,
+                                                       const int* __restrict__ trig, const int* __restrict__ active,
+                                                       long long n, double radius, const double* __restrict__ part,
+                                                       double* __restrict__ norm_out, int* __restrict__ count) {
+  const int g = blockIdx.y;
+  if (trig[g] < 0 || active[g] == 0) return;
+  double n2 = 0.0;
+  for (int b = 0; b < (int)gridDim.x; ++b) n2 += part[(long long)g * gridDim.x + b];
+  const double nr = sqrt(n2);
+  const bool pull = isfinite(nr) && nr > radius;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    norm_out[g] = nr;
+    if (pull) count[g] = count[g] + 1;
+  }
+  if (!pull) return;
+  const double s = radius / nr;
+  float* wg = w + (long long)g * ws;
+  const float* bg = base + (long long)g * bs;
+  const BallSpan sp(wg, bg, n);
+  const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x, dt = (long long)gridDim.x * blockDim.x;
+  for (long long i = t0; i < sp.nv; i += dt) {
+    float4 a = *reinterpret_cast<const float4*>(wg + sp.h + 4 * i);
+    const float4 b = *reinterpret_cast<const float4*>(bg + sp.h + 4 * i);
+    a.x = ball_pull(a.x, b.x, s);
+    a.y = ball_pull(a.y, b.y, s);
+    a.z = ball_pull(a.z, b.z, s);
+    a.w = ball_pull(a.w, b.w, s);
+    *reinterpret_cast<float4*>(wg + sp.h + 4 * i) = a;
+  }
+  for (long long k = t0; k < n - 4 * sp.nv; k += dt) {
+    const long long e = sp.edge(k);
+    wg[e] = ball_pull(wg[e], bg[e], s);
+  }
+}
+
 }  // namespace
+
+// PGD attacker's per-step projection of the replicas training with a trigger onto the L2 ball of
+// `radius` around base, over the first n entries of each row.  part: [G][256] fp64 workspace (no
+// initialisation needed); norm_out [G] fp64, count [G] int32 (+1 per projection)
+DBA_EXPORT int dba_project_to_ball(float* w, long long ws, const float* base, long long bs, long long n, int G,
+                                   const int* trig, const int* active, double radius, double* norm_out, int* count,
+                                   double* part, void* stream) {
+  const int bx = (int)std::max(1LL, std::min(256LL, (n + 2047) / 2048));
+  hipLaunchKernelGGL(ballnorm_kernel, dim3(bx, G), dim3(256), 0, (hipStream_t)stream, w, ws, base, bs, trig, active, n,
+                     part);
+  hipLaunchKernelGGL(ballproj_kernel, dim3(bx, G), dim3(256), 0, (hipStream_t)stream, w, ws, base, bs, trig, active, n,
+                     radius, part, norm_out, count);
+  DBA_LAUNCH_CHECK();
+}
 
 // part: [G][256] fp32 workspace (no initialisation needed)
 DBA_EXPORT int dba_dist_loss_grad(const float* w, long long ws, const float* base, long long bs, float* grads,

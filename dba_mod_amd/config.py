@@ -171,6 +171,14 @@ _DEFAULTS: Dict[str, Any] = {
     # aggregate, with clip_norm's grammar: None = off; a finite number > 0 = C; "median" = the lower
     # median of the round's client update norms
     "sparse_clip": None,
+    # norm-bounded (PGD) attacker (Sun et al. 2019; Wang et al., NeurIPS 2020): while a client trains
+    # with a trigger its state is projected, after every SGD step, onto the L2 ball of radius
+    # delta / gamma around its phase-start state, over the entries the server aggregates; gamma =
+    # scale_weights_poison when the phase is scaled afterwards (not baseline), else 1, so the update
+    # it submits has norm at most delta.  None = off; a finite number > 0 = delta.  Needs is_poison
+    # and aggr_epoch_interval == 1; not with foolsgold (which aggregates gradient sums).  LOAN then
+    # trains on the per-step graph (the persistent launch has no per-step hook)
+    "poison_pgd_norm": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -236,6 +244,20 @@ class Params(dict):
         if self.sparse_topk is not None and self["diff_privacy"]:
             raise ValueError("sparse_topk cannot be combined with diff_privacy (noise on the dropped "
                              "coordinates undoes the sparsity, noise on the kept ones publishes the support)")
+        if self.poison_pgd_norm is not None:
+            if self["aggregation_methods"] == AGGR_FOOLSGOLD:
+                raise ValueError("poison_pgd_norm cannot be combined with aggregation 'foolsgold' (it aggregates "
+                                 "gradient sums, not state deltas)")
+            if self["aggr_epoch_interval"] != 1:
+                raise ValueError("poison_pgd_norm requires aggr_epoch_interval == 1 (the ball's centre moves at "
+                                 "every phase end: the bound would hold per phase only)")
+            if not self["is_poison"]:
+                raise ValueError("poison_pgd_norm is set without is_poison: true")
+
+    @property
+    def poison_pgd_norm(self) -> Optional[float]:
+        """The checked ``poison_pgd_norm``: None (off) or the bound delta as a float."""
+        return check_pgd_norm(self.get("poison_pgd_norm"))
 
     @property
     def type(self) -> str:
@@ -482,6 +504,15 @@ def check_sparse_topk(v: Any) -> Optional[float]:
     if isinstance(v, float) and 0.0 < v <= 1.0:
         return v
     raise ValueError(f"sparse_topk {v!r}: expected None or a float fraction with 0 < frac <= 1")
+
+
+def check_pgd_norm(v: Any) -> Optional[float]:
+    """None or a finite bound > 0 (returned as float; a bool, a string or a list is an error)."""
+    if v is None:
+        return None
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
+        return float(v)
+    raise ValueError(f"poison_pgd_norm {v!r}: expected None or a finite number > 0")
 
 
 class MeanOption(NamedTuple):

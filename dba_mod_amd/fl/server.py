@@ -595,6 +595,9 @@ class Server:
         interval = int(self.params["aggr_epoch_interval"])
         W = max_slots * 3 + interval * 5
         o_n = max_slots * 3 + interval
+        pgd = self.params.poison_pgd_norm is not None
+        if pgd:       # two more columns: the steps that projected, the last pre-projection norm
+            o_p, W = W, W + 2
         sc = torch.zeros(n, W, dtype=torch.float64)
         for i, c in enumerate(plan.clients):
             r = by_name.get(c.name)
@@ -607,6 +610,8 @@ class Server:
                 nr = r.scale_norms.get(ph.epoch)
                 if nr is not None:
                     sc[i, o_n + 4 * k:o_n + 4 * k + 4] = torch.tensor(nr, dtype=torch.float64)
+            if pgd:
+                sc[i, o_p], sc[i, o_p + 1] = r.pgd_steps, r.pgd_last_norm
         if self.d.enabled:
             scd = sc.to(self.device)
             self.d.all_reduce_(scd)
@@ -618,6 +623,8 @@ class Server:
             norms = {ph.epoch: tuple(float(v) for v in sc[i, o_n + 4 * k:o_n + 4 * k + 4])
                      for k, ph in enumerate(c.phases)}
             cstats[c.name] = {"stats": st, "dist": dists, "norms": norms}
+            if pgd:
+                cstats[c.name]["pgd"] = (int(round(float(sc[i, o_p]))), float(sc[i, o_p + 1]))
         return bank, local_in, cstats
 
     def _reduce(self, t: torch.Tensor) -> torch.Tensor:
@@ -864,6 +871,21 @@ class Server:
             elif kind == "scale_acc":
                 if csv.scale_temp_one_row:
                     csv.scale_temp_one_row.append(round(out.get("global_acc", 0.0), 4))
+        delta = p.poison_pgd_norm
+        if delta is not None:
+            # the norm-bounded attacker's round: one line per poisoning client, the two numbers into
+            # metrics.jsonl (no CSV has a column for them)
+            r = self.trainer.pgd_radius
+            for c in plan.clients:
+                trained = sum(1 for s in c.steps if s.trig >= 0)
+                if not trained:
+                    continue
+                steps, last = cstats[c.name]["pgd"]
+                log.info(f"[pgd] epoch {plan.epoch}, local model {c.name}: delta: {delta}  r: {r}  "
+                         f"gamma: {self.trainer.pgd_gamma}  projected: {steps}/{trained} steps  "
+                         f"last norm before projection: {last}")
+                out.setdefault("pgd", {})[str(c.name)] = {"pgd_steps": steps, "steps": trained,
+                                                          "pgd_last_norm": last}
         if p["is_poison"] and not p["best_on_clean_loss"]:
             out["val_loss"] = out.get("poison_loss", out.get("global_loss"))   # D6
         else:

@@ -58,13 +58,18 @@ class ClientResult:
     # the reference's poison-phase log lines (helper.model_global_norm / model_dist_norm,
     # image_train.py:144-146,172-183; loan_train.py:148-168)
     scale_norms: Dict[int, Tuple[float, float, float, float]] = field(default_factory=dict)
+    # poison_pgd_norm: the steps whose projection moved the client's state, and the distance to the
+    # phase-start state (over the aggregated entries) that its last trigger step reached before
+    # the projection
+    pgd_steps: int = 0
+    pgd_last_norm: float = 0.0
 
 
 class _GroupBuffers:
     """Static per-G buffers (and the captured graph) reused across rounds."""
 
     def __init__(self, spec: ModelSpec, G: int, B: int, max_slots: int, device: torch.device,
-                 fg: bool) -> None:
+                 fg: bool, pgd: bool = False) -> None:
         S, P = spec.S, spec.P
         self.G, self.B, self.max_slots = G, B, max_slots
         self.state = torch.zeros(G, S, dtype=torch.float32, device=device)
@@ -74,6 +79,9 @@ class _GroupBuffers:
         self.base = torch.zeros(G, S, dtype=torch.float32, device=device)   # phase-start states
         self.stats = torch.zeros(3, G * max_slots, dtype=torch.float32, device=device)
         self.nan_flag = torch.zeros(1, dtype=torch.float32, device=device)
+        # poison_pgd_norm: per replica, the last pre-projection distance and the projections made
+        self.pgd_norm = torch.zeros(G, dtype=torch.float64, device=device) if pgd else None
+        self.pgd_count = torch.zeros(G, dtype=torch.int32, device=device) if pgd else None
         # packed descriptor: idx[G*B] poison_n[G] trig[G] first[G] active[G] nvalid[G] slot[G] seed[G] lr[G]
         self.D = G * B + 8 * G
         self.desc = torch.zeros(self.D, dtype=torch.int32, device=device)
@@ -124,8 +132,17 @@ class GroupTrainer:
         # LoanNet: every client's steps between two phase events run in ONE persistent launch
         # (csrc/kernels/mlp.hip, one workgroup per client) instead of a graph replay per step;
         # DBA_MLP_PERSIST=0 keeps the per-step graph
+        # norm-bounded (PGD) attacker: a replica training with a trigger is projected after every
+        # SGD step onto the ball of radius delta / gamma around its phase-start state, over the
+        # entries the server aggregates (gamma: the model-replacement factor the phase end
+        # applies, so the scaled update has norm <= delta); None = off (no launch, no buffers)
+        delta = params.poison_pgd_norm
+        self.pgd_gamma = 1.0 if bool(params["baseline"]) else float(params["scale_weights_poison"])
+        self.pgd_radius: Optional[float] = None if delta is None else delta / self.pgd_gamma
+        self.n_upd = self.spec.S if params["aggregate_bn_buffers"] else self.spec.P
+        # (the persistent launch has no per-step hook for the projection either)
         self.persistent = (self.spec.arch == "loan" and self.device.type == "cuda" and self.alpha == 1.0
-                           and not self.trace and ops.backend_name(self.device) == "hip"
+                           and self.pgd_radius is None and not self.trace and ops.backend_name(self.device) == "hip"
                            and os.environ.get("DBA_MLP_PERSIST", "1") != "0")
         # per-client epoch slots of the step statistics: sized once for the longest phase the
         # config can run (benign and poison rounds then share one buffer set and one captured
@@ -174,6 +191,9 @@ class GroupTrainer:
             loss = torch.where(b.trig >= 0, self.alpha * loss + (1.0 - self.alpha) * dist, loss)
         ops.sgd_step(b.state[:, :self.spec.P], b.grads, b.mom, b.lr, b.first, b.active, self.momentum,
                      self.wd, fg_accum=b.fg)
+        if self.pgd_radius is not None:
+            ops.project_to_ball(b.state, b.base, self.n_upd, b.trig, b.active, self.pgd_radius, b.pgd_norm,
+                                b.pgd_count)
         if not fused:
             ref_ops.accumulate_step_stats(b.stats, b.slot, loss, correct, b.nvalid)
         self._last_loss = loss
@@ -181,7 +201,8 @@ class GroupTrainer:
     def _buffers(self, G: int, max_slots: int) -> _GroupBuffers:
         key = (G, max_slots)
         if key not in self._bufs:
-            self._bufs[key] = _GroupBuffers(self.spec, G, self.B, max_slots, self.device, self.fg)
+            self._bufs[key] = _GroupBuffers(self.spec, G, self.B, max_slots, self.device, self.fg,
+                                            self.pgd_radius is not None)
         return self._bufs[key]
 
     def prewarm(self, G: int) -> None:
@@ -370,6 +391,9 @@ class GroupTrainer:
             dst.fg[j].copy_(src.fg[i])
         ms = dst.max_slots
         dst.stats.view(3, -1, ms)[:, j].copy_(src.stats.view(3, -1, ms)[:, i])
+        if dst.pgd_count is not None:
+            dst.pgd_norm[j].copy_(src.pgd_norm[i])
+            dst.pgd_count[j].copy_(src.pgd_count[i])
 
     def _wave_collect(self, w: Optional[Dict[str, Any]]) -> List[ClientResult]:
         if w is None:
@@ -391,11 +415,14 @@ class GroupTrainer:
             dists[g][e] = float(v[0])
             norms[g][e] = (v[1], v[2], v[3], v[4])
         tr = w["trace"].cpu().numpy() if w["trace"] is not None else None    # [T, G, 2]
+        pgd_n = b.pgd_norm.tolist() if b.pgd_norm is not None else [0.0] * G
+        pgd_c = b.pgd_count.tolist() if b.pgd_count is not None else [0] * G
         for g, c in enumerate(clients):
             nsl = sum(ph.internal_epochs for ph in c.phases)
             res.append(ClientResult(c.name, snaps[g], b.fg[g].clone() if b.fg is not None else None,
                                     stats[g, :nsl].copy(), dists[g], c.num_samples, len(c.steps),
-                                    tr[:len(c.steps), g].copy() if tr is not None else None, norms[g]))
+                                    tr[:len(c.steps), g].copy() if tr is not None else None, norms[g],
+                                    int(pgd_c[g]), float(pgd_n[g])))
         return res
 
     def _reset(self, b: _GroupBuffers, global_state: torch.Tensor) -> None:
@@ -406,6 +433,9 @@ class GroupTrainer:
         b.nan_flag.zero_()
         if b.fg is not None:
             b.fg.zero_()
+        if b.pgd_count is not None:
+            b.pgd_norm.zero_()
+            b.pgd_count.zero_()
 
     def _zeros_p(self) -> torch.Tensor:
         z = getattr(self, "_zp", None)

@@ -91,6 +91,7 @@ _SIGS = {
     "dba_topk_select": [_P, _P, _LL, _LL, _P, _P, _P],
     "dba_topk_apply": [_P, _P, _P, _LL, _F, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
+    "dba_project_to_ball": [_P, _LL, _P, _LL, _LL, _I, _P, _P, _D, _P, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
     "dba_xwgrad_halo_set": [_I],
@@ -1304,6 +1305,20 @@ def dist_loss_grad(w, base, grads, trig, active, alpha):
     _call("dba_dist_loss_grad", w.data_ptr(), w.stride(0), base.data_ptr(), base.stride(0), grads.data_ptr(), P, G,
           _i32(trig).data_ptr(), _i32(active).data_ptr(), float(alpha), nrm2.data_ptr(), part.data_ptr(), _stream())
     return nrm2.sqrt()
+
+
+def project_to_ball(w, base, n, trig, active, radius, norm_out, count):
+    G, n = w.shape[0], int(n)
+    assert w.dtype == _F32 and base.dtype == _F32 and w.dim() == 2 and base.dim() == 2
+    assert w.stride(1) == 1 and base.stride(1) == 1 and base.shape[0] >= G
+    assert 1 <= n <= w.shape[1] and n <= base.shape[1]
+    assert trig.dtype == torch.int32 and active.dtype == torch.int32 and trig.is_contiguous() and active.is_contiguous()
+    assert trig.numel() >= G and active.numel() >= G
+    assert norm_out.dtype == torch.float64 and norm_out.is_contiguous() and norm_out.numel() >= G
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= G
+    part = torch.empty(G, 256, dtype=torch.float64, device=w.device)
+    _call("dba_project_to_ball", w.data_ptr(), w.stride(0), base.data_ptr(), base.stride(0), n, G, trig.data_ptr(),
+          active.data_ptr(), float(radius), norm_out.data_ptr(), count.data_ptr(), part.data_ptr(), _stream())
 
 
 # ---------------------------------------------------------------- flat / aggregation

@@ -12,6 +12,7 @@ cross-entropy mean/sum reductions, ``torch.optim.SGD`` with momentum + weight de
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -510,6 +511,29 @@ def dist_loss_grad(w: Tensor, base: Tensor, grads: Tensor, trig: Tensor, active:
         c = (1.0 - alpha) / nr if float(nr) > 0 else 0.0
         grads[g] = alpha * grads[g] + c * d
     return out
+
+
+def project_to_ball(w: Tensor, base: Tensor, n: int, trig: Tensor, active: Tensor, radius: float,
+                    norm_out: Tensor, count: Tensor) -> None:
+    """The norm-bounded (PGD) attacker's per-step projection (Sun et al. 2019; Wang et al. 2020).
+
+    For replicas training with a trigger (``trig >= 0`` and active): ``norm_out[g]`` (fp64) :=
+    ``||w[g, :n] - base[g, :n]||`` in fp64; where that norm is finite and ``> radius`` (strict),
+    ``w[g, :n] := base + (radius / norm)(w - base)`` computed in fp64 and rounded once, and
+    ``count[g] += 1``.  Nothing else is written: other replicas, a replica whose norm is within
+    the radius or not finite, and entries at and past ``n`` keep their bits.
+    """
+    for g in range(w.shape[0]):
+        if int(trig[g]) < 0 or int(active[g]) == 0:
+            continue
+        b = base[g, :n].double()
+        d = w[g, :n].double() - b
+        nr = torch.sqrt((d * d).sum())
+        norm_out[g] = nr
+        nrf = float(nr)
+        if math.isfinite(nrf) and nrf > radius:
+            w[g, :n] = (b + (radius / nrf) * d).float()
+            count[g] += 1
 
 
 # ---------------------------------------------------------------- flat / aggregation

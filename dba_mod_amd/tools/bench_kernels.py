@@ -561,6 +561,72 @@ def _bench_topk(name, L, frac, reps, dev):
     return out
 
 
+# the PGD attacker's per-step projection (flat.hip): the CIFAR model's aggregated entries, a lone
+# attacker (the solo tail's G = 1 graph) and a full group of 10
+PGD = [("pgd.cifar.g1", 1, 2_802_430), ("pgd.cifar.g10", 10, 2_802_430)]
+
+
+def _bench_pgd(name, G, n, reps, dev, rounds=5, inner=10):
+    """``project_to_ball`` with every replica projecting, against ``dist_loss_grad`` at the same n and
+    G: the same two-launch shape (per-block partials of ||w - base||^2, then an element-wise pass that
+    sums them).  Past the norm launch's w and base, dist_loss_grad's second launch moves 4 streams of n
+    floats (w, base and grads in, grads out) and the projection's 3 (w and base in, w out): 6 to 5
+    over the two launches (GB/s counts those), 4 to 3 in the element-wise pass alone.  A projected
+    state does not project again, so one timed graph restores w (a copy, timed on its own and
+    subtracted) and makes ``inner`` calls with radii shrinking by 1 % each: all of them project
+    (checked on the counter).  The two are timed in turn, ``rounds`` times over: medians and
+    min .. max.  The rows are [G, n] views of buffers 4-float aligned in width, so every row takes
+    the float4 body.  dist_loss_grad is launched on preallocated outputs (its wrapper's zero fill and
+    square root are not timed)."""
+    torch.manual_seed(0)
+    stride = (n + 3) // 4 * 4
+    base = torch.randn(G, stride, device=dev)[:, :n]
+    w0 = (base + 0.01 * torch.randn(G, n, device=dev))
+    w = torch.zeros(G, stride, device=dev)[:, :n]
+    grads = torch.randn(G, n, device=dev)
+    trig = torch.zeros(G, dtype=torch.int32, device=dev)
+    one = torch.ones(G, dtype=torch.int32, device=dev)
+    norm = torch.zeros(G, dtype=torch.float64, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    r0 = 0.5 * float(torch.linalg.vector_norm((w0[0] - base[0]).double()))
+
+    def restore():
+        w.copy_(w0)
+
+    def projections():
+        restore()
+        for k in range(inner):
+            H.project_to_ball(w, base, n, trig, one, r0 * 0.99 ** k, norm, count)
+
+    projections()
+    assert count.tolist() == [inner] * G, count.tolist()
+    w.copy_(w0)
+    nrm2 = torch.zeros(G, device=dev)
+    part = torch.empty(G, 256, device=dev)
+
+    def dist():
+        H._call("dba_dist_loss_grad", w.data_ptr(), w.stride(0), base.data_ptr(), base.stride(0), grads.data_ptr(), n, G,
+                trig.data_ptr(), one.data_ptr(), 0.7, nrm2.data_ptr(), part.data_ptr(), H._stream())
+
+    fns = {"project": lambda: _time(projections, reps, inner=1), "restore": lambda: _time(restore, reps, inner=1),
+           "dist_loss_grad": lambda: _time(dist, reps, inner=inner)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(fn())
+    times["project"] = [(p - c) / inner for p, c in zip(times["project"], times["restore"])]
+    out = {"shape": name, "G": G, "n": n, "rounds": rounds}
+    for k, streams in (("project", 5), ("dist_loss_grad", 6)):
+        v = sorted(times[k])
+        med = v[len(v) // 2]
+        out.update({f"{k}_us": round(med * 1e6, 2), f"{k}_min_us": round(v[0] * 1e6, 2),
+                    f"{k}_max_us": round(v[-1] * 1e6, 2), f"{k}_GBps": round(streams * G * n * 4 / med / 1e9, 1)})
+    out["restore_us"] = round(sorted(times["restore"])[rounds // 2] * 1e6, 2)
+    out["project_vs_dist_loss_grad"] = round(out["project_us"] / out["dist_loss_grad_us"], 3)
+    out["yardstick"] = 1.25
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -613,6 +679,10 @@ def main(argv=None) -> int:
     for name, L, frac in TOPK:
         if args.only in name:
             rows.append(_bench_topk(name, L, frac, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, G, n in PGD:
+        if args.only in name:
+            rows.append(_bench_pgd(name, G, n, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
