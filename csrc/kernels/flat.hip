@@ -278,6 +278,45 @@ __global__ __launch_bounds__(256) void ballproj_kernel(float* __restrict__ w, lo
   }
 }
 
+// Neurotoxin attacker's per-step restore (replicas training with a trigger only): every one of the
+// first n entries whose bit in the keep mask is 0 goes back to its phase-start value, w = base, a
+// copy; a kept entry is neither read nor written.  mask: bit j % 64 of word j / 64 belongs to entry
+// j (nmask.hip).  A lane reads the four bits of its float4 first: all kept costs nothing more, all
+// dropped is one 16-byte load and store, a mix copies entry by entry.  w is never read.  Thread
+// (0, g) counts the step
+__global__ __launch_bounds__(256) void maskrestore_kernel(float* __restrict__ w, long long ws,
+                                                          const float* __restrict__ base, long long bs,
+                                                          const int* __restrict__ trig, const int* __restrict__ active,
+                                                          long long n, const unsigned long long* __restrict__ mask,
+                                                          int* __restrict__ count) {
+  const int g = blockIdx.y;
+  if (trig[g] < 0 || active[g] == 0) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) count[g] = count[g] + 1;
+  float* wg = w + (long long)g * ws;
+  const float* bg = base + (long long)g * bs;
+  const BallSpan sp(wg, bg, n);
+  const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x, dt = (long long)gridDim.x * blockDim.x;
+  for (long long i = t0; i < sp.nv; i += dt) {
+    const long long j = sp.h + 4 * i;       // entries j .. j + 3 < n: the word of j + 3 exists
+    const int sh = (int)(j & 63);
+    unsigned long long m = mask[j >> 6] >> sh;
+    if (sh > 60) m |= mask[(j >> 6) + 1] << (64 - sh);
+    const unsigned keep = (unsigned)m & 15u;
+    if (keep == 15u) continue;
+    if (keep == 0u) {
+      *reinterpret_cast<float4*>(wg + j) = *reinterpret_cast<const float4*>(bg + j);
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (!((keep >> c) & 1u)) wg[j + c] = bg[j + c];
+  }
+  for (long long k = t0; k < n - 4 * sp.nv; k += dt) {
+    const long long e = sp.edge(k);
+    if (!((mask[e >> 6] >> (e & 63)) & 1ull)) wg[e] = bg[e];
+  }
+}
+
 }  // namespace
 
 // PGD attacker's per-step projection of the replicas training with a trigger onto the L2 ball of
@@ -291,6 +330,18 @@ DBA_EXPORT int dba_project_to_ball(float* w, long long ws, const float* base, lo
                      part);
   hipLaunchKernelGGL(ballproj_kernel, dim3(bx, G), dim3(256), 0, (hipStream_t)stream, w, ws, base, bs, trig, active, n,
                      radius, part, norm_out, count);
+  DBA_LAUNCH_CHECK();
+}
+
+// Neurotoxin attacker's per-step restore of the replicas training with a trigger: over the first n
+// entries of each row, w = base where the keep mask's bit is 0.  mask [ceil(n / 64)] int64 words
+// (dba_neurotoxin_mask's); count [G] int32 (+1 per gated-in replica)
+DBA_EXPORT int dba_mask_restore(float* w, long long ws, const float* base, long long bs, long long n, int G,
+                                const int* trig, const int* active, const long long* mask, int* count,
+                                void* stream) {
+  const int bx = (int)std::max(1LL, std::min(256LL, (n + 2047) / 2048));
+  hipLaunchKernelGGL(maskrestore_kernel, dim3(bx, G), dim3(256), 0, (hipStream_t)stream, w, ws, base, bs, trig, active,
+                     n, (const unsigned long long*)mask, count);
   DBA_LAUNCH_CHECK();
 }
 

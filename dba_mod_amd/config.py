@@ -179,6 +179,14 @@ _DEFAULTS: Dict[str, Any] = {
     # and aggr_epoch_interval == 1; not with foolsgold (which aggregates gradient sums).  LOAN then
     # trains on the per-step graph (the persistent launch has no per-step hook)
     "poison_pgd_norm": None,
+    # Neurotoxin attacker (Zhang et al., ICML 2022): while a client trains with a trigger, every
+    # parameter outside a coordinate mask is set back, after every SGD step, to its phase-start
+    # value, so the update it submits is exactly 0 there.  The server rebuilds the mask each round
+    # from the update it just applied: the k = max(1, floor(rho * P)) parameters that moved least
+    # (ties at the threshold all kept), ranked globally.  None = off; a float 0 < rho <= 1 = the kept
+    # fraction (an int is an error, as for sparse_topk).  Needs is_poison and aggr_epoch_interval ==
+    # 1; not with foolsgold (which aggregates gradient sums).  LOAN then trains on the per-step graph
+    "poison_neurotoxin_ratio": None,
     "pretrain_eta": 1.0,
     "pretrain_lr": None,           # client lr of the warm start (None: the config's lr)
     "model_arch": None,            # cifar only: resnet{18,34,50,101,152}_cifar (resnet_cifar.py:106-116);
@@ -253,6 +261,21 @@ class Params(dict):
                                  "every phase end: the bound would hold per phase only)")
             if not self["is_poison"]:
                 raise ValueError("poison_pgd_norm is set without is_poison: true")
+
+        if self.poison_neurotoxin_ratio is not None:
+            if self["aggregation_methods"] == AGGR_FOOLSGOLD:
+                raise ValueError("poison_neurotoxin_ratio cannot be combined with aggregation 'foolsgold' (it "
+                                 "aggregates gradient sums, not state deltas)")
+            if self["aggr_epoch_interval"] != 1:
+                raise ValueError("poison_neurotoxin_ratio requires aggr_epoch_interval == 1 (the restore's base "
+                                 "moves at every phase end: the update would be masked per phase only)")
+            if not self["is_poison"]:
+                raise ValueError("poison_neurotoxin_ratio is set without is_poison: true")
+
+    @property
+    def poison_neurotoxin_ratio(self) -> Optional[float]:
+        """The checked ``poison_neurotoxin_ratio``: None (off) or the kept fraction rho."""
+        return check_neurotoxin_ratio(self.get("poison_neurotoxin_ratio"))
 
     @property
     def poison_pgd_norm(self) -> Optional[float]:
@@ -513,6 +536,16 @@ def check_pgd_norm(v: Any) -> Optional[float]:
     if isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0:
         return float(v)
     raise ValueError(f"poison_pgd_norm {v!r}: expected None or a finite number > 0")
+
+
+def check_neurotoxin_ratio(v: Any) -> Optional[float]:
+    """None or a float fraction with 0 < rho <= 1 (a bool, an int, a string or a list is an error: an
+    int is rejected so that YAML ``1`` cannot be read as the ratio 1.0)."""
+    if v is None:
+        return None
+    if isinstance(v, float) and 0.0 < v <= 1.0:
+        return v
+    raise ValueError(f"poison_neurotoxin_ratio {v!r}: expected None or a float fraction with 0 < rho <= 1")
 
 
 class MeanOption(NamedTuple):

@@ -11,6 +11,7 @@ from __future__ import annotations
 import dataclasses
 import datetime
 import logging
+import math
 import os
 import time
 from typing import Any, Dict, List, Optional, Tuple
@@ -129,6 +130,20 @@ class Server:
                                     max_groups=int(params.get("max_concurrent_clients", 16)))
         self.evaluator = Evaluator(self.wl, self.dtype, chunk=int(params["eval_batch_size"]),
                                    max_groups=int(params.get("eval_max_groups", 24)))
+        # Neurotoxin attacker (poison_neurotoxin_ratio): the keep mask lives in the trainer (one buffer,
+        # rewritten in place after each aggregation); until one exists (a fresh run, the round after
+        # the warm start, an .aux without one) it is "all kept" and the attackers train unconstrained
+        self.ntx_ratio = params.poison_neurotoxin_ratio
+        self.ntx_have_mask = False
+        self._ntx_old: Optional[torch.Tensor] = None     # the round-start parameters, for the mask build
+        self._warm_start = False
+        if self.ntx_ratio is not None and getattr(self, "_ntx_aux", None) is not None:
+            m = self._ntx_aux.to(self.device, torch.int64).reshape(-1)
+            if m.numel() != self.trainer.ntx_mask.numel():
+                raise ValueError(f"neurotoxin_mask of the resumed .aux has {m.numel()} words, this model needs "
+                                 f"{self.trainer.ntx_mask.numel()}")
+            self.trainer.ntx_mask.copy_(m)       # (every rank: the mask is held redundantly)
+            self.ntx_have_mask = True
         self.fg = agg.FoolsGold(bool(params["fg_use_memory"]))
         if getattr(self, "_fg_aux", None):
             self.fg.load_state(self._fg_aux)
@@ -194,6 +209,7 @@ class Server:
                 self._fg_aux = aux.get("foolsgold")
                 if aux.get("sparse_residual") is not None:     # (every rank: the residual is held redundantly)
                     self.sparse_residual = aux["sparse_residual"].to(self.device, torch.float64)
+                self._ntx_aux = aux.get("neurotoxin_mask")
         else:
             flat = self.spec.init_flat(int(p["seed"]))
             self.start_epoch = int(p.get("start_epoch") or 1)
@@ -225,10 +241,12 @@ class Server:
         p.update(dict.fromkeys(C.MEAN_OPTION_KEYS))
         if lr is not None:
             p["lr"] = float(lr)
+        self._warm_start = True      # (no Neurotoxin mask from these rounds)
         try:
             for e in range(1, rounds + 1):
                 self._train_half(e, evaluate=False)
         finally:
+            self._warm_start = False
             p.update(saved)
             self.timer.reset()
         if self.device.type == "cuda":
@@ -300,7 +318,7 @@ class Server:
             handle = self.trainer.train_async(mine, self.global_state, on_client_done=early)
         return {"epoch": epoch, "plan": plan, "owners": owners, "adversarial": adversarial, "t0": t0,
                 "handle": handle, "early": early, "clients_on_rank": len(mine), "evaluate": evaluate,
-                "load": load}
+                "load": load, "ntx_masked": self.ntx_have_mask}
 
     def _job_images(self, job) -> int:
         return len(self.wl.test_clean_idx if job.kind == "clean" else self.wl.test_poison_idx)
@@ -366,7 +384,22 @@ class Server:
         with self.timer.phase("gather"):
             bank, local, cstats = self._gather(plan, st["owners"], results, early, st.get("evaluate", True))
         with self.timer.phase("aggregate"):
+            masks = self.ntx_ratio is not None and not self._warm_start
+            if masks:       # the round-start parameters (no row of the bank holds them)
+                P = self.spec.P
+                if self._ntx_old is None:
+                    self._ntx_old = torch.empty(P, dtype=torch.float32, device=self.device)
+                self._ntx_old.copy_(self.global_state[:P])
             self._aggregate(plan, bank, local, st["adversarial"])
+            ntx = None
+            if masks:
+                # the Neurotoxin mask for the NEXT round's attackers, from the update just applied.
+                # Enqueued on the training stream, so it lands before the next round's first step;
+                # (T, m) stay on the device until the round is recorded
+                k = max(1, int(math.floor(self.ntx_ratio * P)))
+                sel = ops.neurotoxin_mask(self.global_state, self._ntx_old, P, k, self.trainer.ntx_mask)
+                self.ntx_have_mask = True
+                ntx = {"k": k, "sel": sel, "masked": bool(st.get("ntx_masked", False))}
             bank[0].copy_(self.global_state)
             if p["nan_check"] and not bool(torch.isfinite(self.global_state).all()):
                 # fail fast: a non-finite global model poisons every later round
@@ -375,10 +408,13 @@ class Server:
         # the residual as this round left it, for the round's checkpoint (written in _finish, when
         # a pipelined next round may already have moved it on)
         saves = self.write and p["save_model"] and p.sparse_topk is not None and self.sparse_residual is not None
+        # (the Neurotoxin mask likewise: the next round's aggregation rewrites it in place)
+        saves_ntx = self.write and p["save_model"] and ntx is not None
         return {"epoch": epoch, "plan": plan, "bank": bank, "cstats": cstats, "t0": st["t0"],
                 "clients_on_rank": st["clients_on_rank"], "phases": self.timer.reset(), "early": early,
                 "comm_bytes": self.d.take_bytes(),
-                "sparse_residual": self.sparse_residual.clone() if saves else None}
+                "sparse_residual": self.sparse_residual.clone() if saves else None,
+                "ntx": ntx, "neurotoxin_mask": self.trainer.ntx_mask.clone() if saves_ntx else None}
 
     def _train_half(self, epoch: int, evaluate: bool = True) -> Dict[str, Any]:
         return self._train_end(self._train_begin(epoch, evaluate))
@@ -446,7 +482,9 @@ class Server:
             comm[k] = comm.get(k, 0) + v
         t_io = time.perf_counter()
         summary = self._record(pend["plan"], res, pend["cstats"])
-        self._save_model(pend["epoch"], summary["val_loss"], pend["bank"][0], pend.get("sparse_residual"))
+        self._record_neurotoxin(pend, summary)
+        self._save_model(pend["epoch"], summary["val_loss"], pend["bank"][0], pend.get("sparse_residual"),
+                         pend.get("neurotoxin_mask"))
         self.csv.save(bool(p["is_poison"]))
         now = time.perf_counter()
         phases = dict(pend["phases"])
@@ -598,6 +636,9 @@ class Server:
         pgd = self.params.poison_pgd_norm is not None
         if pgd:       # two more columns: the steps that projected, the last pre-projection norm
             o_p, W = W, W + 2
+        ntx = self.ntx_ratio is not None
+        if ntx:       # one more column: the steps the masked restore ran on
+            o_x, W = W, W + 1
         sc = torch.zeros(n, W, dtype=torch.float64)
         for i, c in enumerate(plan.clients):
             r = by_name.get(c.name)
@@ -612,6 +653,8 @@ class Server:
                     sc[i, o_n + 4 * k:o_n + 4 * k + 4] = torch.tensor(nr, dtype=torch.float64)
             if pgd:
                 sc[i, o_p], sc[i, o_p + 1] = r.pgd_steps, r.pgd_last_norm
+            if ntx:
+                sc[i, o_x] = r.ntx_steps
         if self.d.enabled:
             scd = sc.to(self.device)
             self.d.all_reduce_(scd)
@@ -625,6 +668,8 @@ class Server:
             cstats[c.name] = {"stats": st, "dist": dists, "norms": norms}
             if pgd:
                 cstats[c.name]["pgd"] = (int(round(float(sc[i, o_p]))), float(sc[i, o_p + 1]))
+            if ntx:
+                cstats[c.name]["ntx"] = int(round(float(sc[i, o_x])))
         return bank, local_in, cstats
 
     def _reduce(self, t: torch.Tensor) -> torch.Tensor:
@@ -892,8 +937,33 @@ class Server:
             out["val_loss"] = out.get("global_loss")
         return out
 
+    def _record_neurotoxin(self, pend: Dict[str, Any], out: Dict[str, Any]) -> None:
+        """The Neurotoxin attacker's round: one line for the mask the round built, one per poisoning
+        client; both into the round's metrics.jsonl record (no CSV has a column for them)."""
+        ntx = pend.get("ntx")
+        if ntx is None:
+            return
+        plan, rho, k = pend["plan"], self.ntx_ratio, ntx["k"]
+        T, m = (int(v) for v in ntx["sel"].tolist())
+        thr = float(np.array([T], dtype=np.uint32).view(np.float32)[0])
+        log.info(f"[neurotoxin] epoch {plan.epoch}: mask for the next round: rho: {rho}  k: {k}  kept: {m}/"
+                 f"{self.spec.P}  threshold |update|: {thr}")
+        rec: Dict[str, Any] = {"rho": rho, "k": k, "kept": m, "threshold": thr, "masked": ntx["masked"]}
+        poisoners = [(c, sum(1 for s in c.steps if s.trig >= 0)) for c in plan.clients]
+        poisoners = [(c, n) for c, n in poisoners if n]
+        if poisoners and not ntx["masked"]:
+            log.info(f"[neurotoxin] epoch {plan.epoch}: no mask exists yet (no earlier round of this run built "
+                     f"one): the attackers trained unconstrained")
+        for c, trained in poisoners:
+            steps = pend["cstats"][c.name]["ntx"]
+            log.info(f"[neurotoxin] epoch {plan.epoch}, local model {c.name}: restored after {steps}/{trained} steps"
+                     f"{'' if ntx['masked'] else ' (mask: all kept)'}")
+            rec.setdefault("clients", {})[str(c.name)] = {"ntx_steps": steps, "steps": trained}
+        out["neurotoxin"] = rec
+
     def _save_model(self, epoch: int, val_loss: Optional[float], state: Optional[torch.Tensor] = None,
-                    sparse_residual: Optional[torch.Tensor] = None) -> None:
+                    sparse_residual: Optional[torch.Tensor] = None,
+                    neurotoxin_mask: Optional[torch.Tensor] = None) -> None:
         p = self.params
         if not (self.write and p["save_model"]):
             return
@@ -905,6 +975,8 @@ class Server:
                "epoch": int(epoch)}
         if sparse_residual is not None:      # (sparse_topk runs only: other runs' .aux keep their keys)
             aux["sparse_residual"] = sparse_residual.detach().to("cpu", torch.float64)
+        if neurotoxin_mask is not None:      # (poison_neurotoxin_ratio runs only)
+            aux["neurotoxin_mask"] = neurotoxin_mask.detach().to("cpu", torch.int64)
         ckpt.save_aux(name + ".aux", aux)
         if epoch in list(p["save_on_epochs"] or []):
             log.info(f"Saving model on epoch {epoch}")

@@ -63,13 +63,15 @@ class ClientResult:
     # the projection
     pgd_steps: int = 0
     pgd_last_norm: float = 0.0
+    # poison_neurotoxin_ratio: the steps after which the masked restore ran for the client
+    ntx_steps: int = 0
 
 
 class _GroupBuffers:
     """Static per-G buffers (and the captured graph) reused across rounds."""
 
     def __init__(self, spec: ModelSpec, G: int, B: int, max_slots: int, device: torch.device,
-                 fg: bool, pgd: bool = False) -> None:
+                 fg: bool, pgd: bool = False, ntx: bool = False) -> None:
         S, P = spec.S, spec.P
         self.G, self.B, self.max_slots = G, B, max_slots
         self.state = torch.zeros(G, S, dtype=torch.float32, device=device)
@@ -82,6 +84,8 @@ class _GroupBuffers:
         # poison_pgd_norm: per replica, the last pre-projection distance and the projections made
         self.pgd_norm = torch.zeros(G, dtype=torch.float64, device=device) if pgd else None
         self.pgd_count = torch.zeros(G, dtype=torch.int32, device=device) if pgd else None
+        # poison_neurotoxin_ratio: per replica, the steps the masked restore ran on
+        self.ntx_count = torch.zeros(G, dtype=torch.int32, device=device) if ntx else None
         # packed descriptor: idx[G*B] poison_n[G] trig[G] first[G] active[G] nvalid[G] slot[G] seed[G] lr[G]
         self.D = G * B + 8 * G
         self.desc = torch.zeros(self.D, dtype=torch.int32, device=device)
@@ -140,9 +144,18 @@ class GroupTrainer:
         self.pgd_gamma = 1.0 if bool(params["baseline"]) else float(params["scale_weights_poison"])
         self.pgd_radius: Optional[float] = None if delta is None else delta / self.pgd_gamma
         self.n_upd = self.spec.S if params["aggregate_bn_buffers"] else self.spec.P
-        # (the persistent launch has no per-step hook for the projection either)
+        # Neurotoxin attacker: after every SGD step a replica training with a trigger gets every
+        # parameter outside the keep mask set back to its phase-start value.  The mask is ONE buffer
+        # per trainer (int64 words, bit j % 64 of word j // 64 = parameter j), it starts as "all kept"
+        # and the server rewrites it in place after each aggregation, on the training stream: the
+        # captured graphs keep its pointer, nothing is re-captured.  None = off (no launch, no buffer)
+        self.ntx_ratio: Optional[float] = params.poison_neurotoxin_ratio
+        self.ntx_mask: Optional[torch.Tensor] = (
+            None if self.ntx_ratio is None else ref_ops.neurotoxin_all_kept(self.spec.P, self.device))
+        # (the persistent launch has no per-step hook for the projection or the restore either)
         self.persistent = (self.spec.arch == "loan" and self.device.type == "cuda" and self.alpha == 1.0
-                           and self.pgd_radius is None and not self.trace and ops.backend_name(self.device) == "hip"
+                           and self.pgd_radius is None and self.ntx_ratio is None and not self.trace
+                           and ops.backend_name(self.device) == "hip"
                            and os.environ.get("DBA_MLP_PERSIST", "1") != "0")
         # per-client epoch slots of the step statistics: sized once for the longest phase the
         # config can run (benign and poison rounds then share one buffer set and one captured
@@ -191,6 +204,8 @@ class GroupTrainer:
             loss = torch.where(b.trig >= 0, self.alpha * loss + (1.0 - self.alpha) * dist, loss)
         ops.sgd_step(b.state[:, :self.spec.P], b.grads, b.mom, b.lr, b.first, b.active, self.momentum,
                      self.wd, fg_accum=b.fg)
+        if self.ntx_mask is not None:
+            ops.mask_restore(b.state, b.base, self.spec.P, b.trig, b.active, self.ntx_mask, b.ntx_count)
         if self.pgd_radius is not None:
             ops.project_to_ball(b.state, b.base, self.n_upd, b.trig, b.active, self.pgd_radius, b.pgd_norm,
                                 b.pgd_count)
@@ -202,7 +217,7 @@ class GroupTrainer:
         key = (G, max_slots)
         if key not in self._bufs:
             self._bufs[key] = _GroupBuffers(self.spec, G, self.B, max_slots, self.device, self.fg,
-                                            self.pgd_radius is not None)
+                                            self.pgd_radius is not None, self.ntx_mask is not None)
         return self._bufs[key]
 
     def prewarm(self, G: int) -> None:
@@ -394,6 +409,8 @@ class GroupTrainer:
         if dst.pgd_count is not None:
             dst.pgd_norm[j].copy_(src.pgd_norm[i])
             dst.pgd_count[j].copy_(src.pgd_count[i])
+        if dst.ntx_count is not None:
+            dst.ntx_count[j].copy_(src.ntx_count[i])
 
     def _wave_collect(self, w: Optional[Dict[str, Any]]) -> List[ClientResult]:
         if w is None:
@@ -417,12 +434,13 @@ class GroupTrainer:
         tr = w["trace"].cpu().numpy() if w["trace"] is not None else None    # [T, G, 2]
         pgd_n = b.pgd_norm.tolist() if b.pgd_norm is not None else [0.0] * G
         pgd_c = b.pgd_count.tolist() if b.pgd_count is not None else [0] * G
+        ntx_c = b.ntx_count.tolist() if b.ntx_count is not None else [0] * G
         for g, c in enumerate(clients):
             nsl = sum(ph.internal_epochs for ph in c.phases)
             res.append(ClientResult(c.name, snaps[g], b.fg[g].clone() if b.fg is not None else None,
                                     stats[g, :nsl].copy(), dists[g], c.num_samples, len(c.steps),
                                     tr[:len(c.steps), g].copy() if tr is not None else None, norms[g],
-                                    int(pgd_c[g]), float(pgd_n[g])))
+                                    int(pgd_c[g]), float(pgd_n[g]), int(ntx_c[g])))
         return res
 
     def _reset(self, b: _GroupBuffers, global_state: torch.Tensor) -> None:
@@ -436,6 +454,8 @@ class GroupTrainer:
         if b.pgd_count is not None:
             b.pgd_norm.zero_()
             b.pgd_count.zero_()
+        if b.ntx_count is not None:
+            b.ntx_count.zero_()
 
     def _zeros_p(self) -> torch.Tensor:
         z = getattr(self, "_zp", None)

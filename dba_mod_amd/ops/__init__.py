@@ -52,6 +52,7 @@ def _dispatch(name: str):
 
 _OPS = ["gather_images", "gather_rows", "conv2d", "conv2d_dgrad", "conv2d_wgrad", "relu_mask_bwd", "bn_fold", "maxpool2d", "maxpool2d_bwd", "avgpool_global",
         "avgpool_global_bwd", "dropout", "dropout_bwd", "softmax_xent", "sgd_step", "dist_loss_grad", "project_to_ball",
+        "neurotoxin_mask", "mask_restore",
         "scale_from_base", "add_noise_scaled", "delta_sum", "sq_dists", "weighted_sum", "weighted_sum_fixed", "delta_stats", "clipped_delta_sum_fixed",
         "clipped_delta_sum", "pairwise_sq_dists", "delta_gram", "trimmed_delta_sum", "bulyan_delta_sum", "delta_sum_votes",
         "vote_agreement", "rlr_apply", "topk_threshold", "topk_apply", "gram", "prepare_dgrad_weights", "wgrad_flush",

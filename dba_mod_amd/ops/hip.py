@@ -92,6 +92,13 @@ _SIGS = {
     "dba_topk_apply": [_P, _P, _P, _LL, _F, _P, _P],
     "dba_dist_loss_grad": [_P, _LL, _P, _LL, _P, _LL, _I, _P, _P, _F, _P, _P, _P],
     "dba_project_to_ball": [_P, _LL, _P, _LL, _LL, _I, _P, _P, _D, _P, _P, _P, _P],
+    # Neurotoxin attacker: the server-side keep mask (csrc/kernels/nmask.hip), the per-step restore (flat.hip)
+    "dba_nmask_blocks": [_LL],
+    "dba_nmask_block_sweep": [],
+    "dba_nmask_blocks_max": [],
+    "dba_nmask_ws_words": [],
+    "dba_neurotoxin_mask": [_P, _P, _LL, _LL, _P, _P, _P, _P],
+    "dba_mask_restore": [_P, _LL, _P, _LL, _LL, _I, _P, _P, _P, _P, _P],
     # reference-precision (fp32) family: csrc/kernels/xconv*.hip, xwgrad.hip, xbn.hip, xaux.hip
     "dba_ximg_set": [_I],
     "dba_xwgrad_halo_set": [_I],
@@ -1319,6 +1326,46 @@ def project_to_ball(w, base, n, trig, active, radius, norm_out, count):
     part = torch.empty(G, 256, dtype=torch.float64, device=w.device)
     _call("dba_project_to_ball", w.data_ptr(), w.stride(0), base.data_ptr(), base.stride(0), n, G, trig.data_ptr(),
           active.data_ptr(), float(radius), norm_out.data_ptr(), count.data_ptr(), part.data_ptr(), _stream())
+
+
+def nmask_geometry() -> Tuple[int, int]:
+    """(coordinates one block of nmask.hip takes per sweep of the grid, the most blocks a launch has):
+    the lengths at which its grid-stride loops change shape (the tests are sized from them)."""
+    return int(_L.dba_nmask_block_sweep()), int(_L.dba_nmask_blocks_max())
+
+
+def neurotoxin_workspace(device) -> Tensor:
+    """The int64 workspace of :func:`neurotoxin_mask` (nmask.hip: the passes' histograms and the
+    select's running state).  It needs no initialisation and carries nothing between calls."""
+    return torch.empty(int(_L.dba_nmask_ws_words()), dtype=torch.int64, device=device)
+
+
+def neurotoxin_mask(w_new, w_old, P, k, mask_words, ws=None):
+    """``mask_words`` int64 [ceil(P / 64)] := the keep mask of the k smallest ``|w_new - w_old|`` over
+    the first P entries; returns ``sel`` int64 [2] on the device = (T, m) (nmask.hip: a 4 x 8-bit
+    radix select from the bottom, the histograms integer adds, no host read; the words are the
+    waves' 64-lane ballots).  ``ws``: a :func:`neurotoxin_workspace` to reuse (default: a fresh one)."""
+    P, k = _ref.neurotoxin_check(w_new, w_old, P, k, mask_words)
+    assert w_new.is_cuda and w_old.device == w_new.device and mask_words.device == w_new.device
+    sel = torch.zeros(2, dtype=torch.int64, device=w_new.device)
+    ws = neurotoxin_workspace(w_new.device) if ws is None else ws
+    assert ws.dtype == torch.int64 and ws.numel() >= int(_L.dba_nmask_ws_words()) and ws.is_contiguous()
+    _call("dba_neurotoxin_mask", w_new.data_ptr(), w_old.data_ptr(), P, k, mask_words.data_ptr(), sel.data_ptr(),
+          ws.data_ptr(), _stream())
+    return sel
+
+
+def mask_restore(w, base, P, trig, active, mask_words, count):
+    G, P = w.shape[0], int(P)
+    assert w.dtype == _F32 and base.dtype == _F32 and w.dim() == 2 and base.dim() == 2
+    assert w.stride(1) == 1 and base.stride(1) == 1 and base.shape[0] >= G
+    assert 1 <= P <= w.shape[1] and P <= base.shape[1]
+    assert trig.dtype == torch.int32 and active.dtype == torch.int32 and trig.is_contiguous() and active.is_contiguous()
+    assert trig.numel() >= G and active.numel() >= G
+    assert mask_words.dtype == torch.int64 and mask_words.is_contiguous() and mask_words.numel() >= (P + 63) // 64
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= G
+    _call("dba_mask_restore", w.data_ptr(), w.stride(0), base.data_ptr(), base.stride(0), P, G, trig.data_ptr(),
+          active.data_ptr(), mask_words.data_ptr(), count.data_ptr(), _stream())
 
 
 # ---------------------------------------------------------------- flat / aggregation

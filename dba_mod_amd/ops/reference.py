@@ -15,6 +15,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -534,6 +535,84 @@ def project_to_ball(w: Tensor, base: Tensor, n: int, trig: Tensor, active: Tenso
         if math.isfinite(nrf) and nrf > radius:
             w[g, :n] = (b + (radius / nrf) * d).float()
             count[g] += 1
+
+
+def neurotoxin_all_kept(P: int, device=None) -> Tensor:
+    """The mask that keeps every one of P coordinates: int64 [ceil(P / 64)], bits at and past P zero."""
+    nw = (int(P) + 63) // 64
+    m = torch.full((nw,), -1, dtype=torch.int64)
+    if P % 64:
+        m[-1] = (1 << (P % 64)) - 1
+    return m.to(device) if device is not None else m
+
+
+def neurotoxin_keys(w_new: Tensor, w_old: Tensor, P: int) -> Tensor:
+    """The select keys of the Neurotoxin mask: the bits of ``u = w_new[:P] - w_old[:P]`` (one fp32
+    subtraction) with the sign bit cleared, as (non-negative) int32.  Integer order is magnitude
+    order: -0 and +0 are 0, denormals order, inf ranks above every finite value and a NaN above inf."""
+    return (w_new[:P] - w_old[:P]).view(torch.int32) & 0x7FFFFFFF
+
+
+def neurotoxin_check(w_new: Tensor, w_old: Tensor, P, k, mask_words: Tensor) -> Tuple[int, int]:
+    """(P, k) of :func:`neurotoxin_mask`, checked the same way on every backend: contiguous fp32
+    vectors of at least P entries, int64 mask words, ``k`` an integer with 1 <= k <= P."""
+    P = int(P)
+    assert w_new.dim() == 1 and w_old.dim() == 1 and w_new.dtype == torch.float32 and w_old.dtype == torch.float32
+    assert w_new.is_contiguous() and w_old.is_contiguous()
+    assert 1 <= P <= w_new.numel() and P <= w_old.numel(), (P, w_new.numel(), w_old.numel())
+    assert mask_words.dtype == torch.int64 and mask_words.is_contiguous() and mask_words.numel() >= (P + 63) // 64
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"neurotoxin_mask: k {k!r}: expected an integer")
+    if not 1 <= k <= P:
+        raise ValueError(f"neurotoxin_mask: k {k} needs 1 <= k <= P = {P}")
+    return P, k
+
+
+def _pack_bits(keep: Tensor) -> Tensor:
+    """bool [P] -> int64 [ceil(P / 64)], bit j % 64 of word j / 64 = keep[j], the tail bits 0."""
+    P = keep.numel()
+    nw = (P + 63) // 64
+    bits = np.zeros(nw * 64, dtype=np.uint8)
+    bits[:P] = keep.cpu().numpy()
+    return torch.from_numpy(np.packbits(bits, bitorder="little").view("<i8").copy())
+
+
+def neurotoxin_kept(mask_words: Tensor, P: int) -> Tensor:
+    """bool [P] on the CPU: coordinate j's bit of the keep mask (:func:`neurotoxin_mask`)."""
+    by = mask_words.detach().cpu().contiguous().numpy().view(np.uint8)
+    return torch.from_numpy(np.unpackbits(by, bitorder="little")[:P].astype(np.bool_))
+
+
+def neurotoxin_mask(w_new: Tensor, w_old: Tensor, P: int, k: int, mask_words: Tensor,
+                    ws: Optional[Tensor] = None) -> Tensor:
+    """The Neurotoxin attacker's coordinate mask (Zhang et al., ICML 2022; nmask.hip is the GPU form),
+    from the update the server applied: with T the k-th smallest of :func:`neurotoxin_keys`,
+    coordinate j < P is kept iff ``key[j] <= T`` (ties at T all kept, so m >= k are).  The first
+    ``ceil(P / 64)`` of ``mask_words`` (int64) are rewritten in place: bit ``j % 64`` of word ``j //
+    64`` is 1 when j is kept, bits at and past P are 0.  Returns ``sel`` int64 [2] on the vectors'
+    device = (T, m).  1 <= k <= P or a ValueError.  ``ws``: a workspace the GPU form can reuse."""
+    P, k = neurotoxin_check(w_new, w_old, P, k, mask_words)
+    keys = neurotoxin_keys(w_new, w_old, P)
+    T = torch.kthvalue(keys.cpu(), k).values
+    keep = keys.cpu() <= T
+    mask_words[:(P + 63) // 64] = _pack_bits(keep).to(mask_words.device)
+    return torch.stack([T.to(torch.int64), keep.sum()]).to(w_new.device)
+
+
+def mask_restore(w: Tensor, base: Tensor, P: int, trig: Tensor, active: Tensor, mask_words: Tensor,
+                 count: Tensor) -> None:
+    """The Neurotoxin attacker's per-step restore.  For replicas training with a trigger (``trig >=
+    0`` and active): every entry ``j < P`` whose bit in ``mask_words`` (:func:`neurotoxin_mask`) is 0
+    is set back to ``base[g, j]``, a copy, and ``count[g] += 1``.  Nothing else is written: kept
+    entries, entries at and past ``P`` and the other replicas keep their bits."""
+    keep = None
+    for g in range(w.shape[0]):
+        if int(trig[g]) < 0 or int(active[g]) == 0:
+            continue
+        if keep is None:
+            keep = neurotoxin_kept(mask_words, P).to(w.device)
+        w[g, :P] = torch.where(keep, w[g, :P], base[g, :P])
+        count[g] += 1
 
 
 # ---------------------------------------------------------------- flat / aggregation

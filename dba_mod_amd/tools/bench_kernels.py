@@ -627,6 +627,74 @@ def _bench_pgd(name, G, n, reps, dev, rounds=5, inner=10):
     return out
 
 
+# the Neurotoxin attacker's two ops at the CIFAR model's P = 2,797,610 parameters: the per-step
+# restore (flat.hip) for a lone attacker and a full group of 10, the server's mask build (nmask.hip)
+NTX_P = 2_797_610
+NTX_RESTORE = [("ntx.restore.cifar.g1", 1, NTX_P), ("ntx.restore.cifar.g10", 10, NTX_P)]
+NTX_MASK = [("ntx.mask.cifar", NTX_P, 0.95)]
+
+
+def _bench_ntx_restore(name, G, n, reps, dev, rho=0.95, rounds=5, inner=10):
+    """``mask_restore`` with every replica gated in, under the rho = 0.95 mask of a random update,
+    against ``project_to_ball`` at the same n and G in the same process (``_bench_pgd``'s row).  The
+    op never reads w and copies a dropped entry whatever w holds, so repeated calls cost the same:
+    ``inner`` calls per timed graph, ``rounds`` times over, the median and min .. max.  It must
+    move the mask (n / 8 bytes per replica) and 8 bytes per dropped entry (base in, w out): GB/s
+    counts those.  Rows are float4-aligned."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    stride = (n + 3) // 4 * 4
+    base = torch.randn(G, stride, device=dev)[:, :n]
+    w = (base + 0.01 * torch.randn(G, n, device=dev))
+    w_old = torch.randn(n, device=dev)
+    w_new = w_old + 0.01 * torch.randn(n, device=dev)
+    k = max(1, int(rho * n))
+    mask = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    kept = int(H.neurotoxin_mask(w_new, w_old, n, k, mask)[1])
+    trig = torch.zeros(G, dtype=torch.int32, device=dev)
+    one = torch.ones(G, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    H.mask_restore(w, base, n, trig, one, mask, count)
+    assert count.tolist() == [1] * G
+    keep = R.neurotoxin_kept(mask, n).to(dev)
+    assert bool((w[:, ~keep] == base[:, ~keep]).all()) and bool((w[:, keep] != base[:, keep]).any())
+    v = sorted(_time(lambda: H.mask_restore(w, base, n, trig, one, mask, count), reps, inner=inner)
+               for _ in range(rounds))
+    med = v[len(v) // 2]
+    moved = G * (n / 8 + 8 * (n - kept))
+    pgd = _bench_pgd(name, G, n, reps, dev, rounds=rounds, inner=inner)
+    return {"shape": name, "G": G, "n": n, "rho": rho, "k": k, "kept": kept, "rounds": rounds,
+            "mask_restore_us": round(med * 1e6, 2), "mask_restore_min_us": round(v[0] * 1e6, 2),
+            "mask_restore_max_us": round(v[-1] * 1e6, 2), "mask_restore_GBps": round(moved / med / 1e9, 1),
+            "project_us": pgd["project_us"], "project_min_us": pgd["project_min_us"],
+            "project_max_us": pgd["project_max_us"],
+            "mask_restore_vs_project": round(med * 1e6 / pgd["project_us"], 3)}
+
+
+def _bench_ntx_mask(name, P, rho, reps, dev, rounds=5):
+    """``neurotoxin_mask`` (the memset, four histogram + scan passes and the ballot pass) on a random
+    update, checked against the ``ops.reference`` form, ``rounds`` times over: the median and
+    min .. max.  Each of its five passes over the coordinates reads w_new and w_old: GB/s counts P * 40
+    bytes."""
+    from dba_mod_amd.ops import reference as R
+    torch.manual_seed(0)
+    w_old = torch.randn(P, device=dev)
+    w_new = w_old + 0.01 * torch.randn(P, device=dev)
+    k = max(1, int(rho * P))
+    nw = (P + 63) // 64
+    mask = torch.empty(nw, dtype=torch.int64, device=dev)
+    ws = H.neurotoxin_workspace(dev)
+    sel = H.neurotoxin_mask(w_new, w_old, P, k, mask, ws)
+    want = torch.empty(nw, dtype=torch.int64)
+    sel_ref = R.neurotoxin_mask(w_new.cpu(), w_old.cpu(), P, k, want)
+    assert sel.tolist() == sel_ref.tolist() and torch.equal(mask.cpu(), want)
+    v = sorted(_time(lambda: H.neurotoxin_mask(w_new, w_old, P, k, mask, ws), reps) for _ in range(rounds))
+    med = v[len(v) // 2]
+    return {"shape": name, "P": P, "rho": rho, "k": k, "kept": int(sel[1]), "rounds": rounds,
+            "mask_us": round(med * 1e6, 1), "mask_min_us": round(v[0] * 1e6, 1), "mask_max_us": round(v[-1] * 1e6, 1),
+            "mask_GBps": round(P * 40 / med / 1e9, 1)}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -683,6 +751,14 @@ def main(argv=None) -> int:
     for name, G, n in PGD:
         if args.only in name:
             rows.append(_bench_pgd(name, G, n, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, G, n in NTX_RESTORE:
+        if args.only in name:
+            rows.append(_bench_ntx_restore(name, G, n, args.reps, dev))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, P, rho in NTX_MASK:
+        if args.only in name:
+            rows.append(_bench_ntx_mask(name, P, rho, args.reps, dev))
             print(json.dumps(rows[-1]), flush=True)
     if args.only in "eval.chunk":
         rows.append(_bench_eval_chunk(17, 1024, max(3, args.reps // 4), dev))
