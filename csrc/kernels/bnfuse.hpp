@@ -101,7 +101,7 @@ __device__ __forceinline__ float bnf_finalize_channel(const BnFuse& f, int g, in
   if (f.mode == 1) {
     const double m = a[0] / n;
     double var = a[1] / n - m * m;
-    var = var > 0 ? var : 0;
+    var = var < 0 ? 0 : var;   // (a NaN stays NaN: `var > 0 ? var : 0` turned it into inv = 1/sqrt(eps))
     const float mean = (float)m, inv = (float)(1.0 / sqrt(var + (double)f.eps));
     float* prm = f.rm_a + (long long)g * f.p_gstride + c;
     float* prv = f.rv_a + (long long)g * f.p_gstride + c;
