@@ -148,7 +148,7 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 //   kind                  tile          vec                    pre              form
 //   1 xconv_kernel        BN (columns)  staging vector 1/4/32  pre-split w      split-K: 0 none, 1 combined in the
 //                                                                               launch, 2 in-block slabs, 3 slabs + reduce
-//   2 xhalo_kernel        image width   Cs                     pre-split w      0
+//   2 xhalo_kernel        image width   Cs                     pre-split w      1 = the fused 1x1 shortcut (SC)
 //   3 ximg_kernel         image width   BN                     pre-split w      0
 //   4 ximg2_kernel        image width   BN                     1                0
 //   5 xstage16_kernel     16            64                     1                0
@@ -156,6 +156,8 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 //   7 xwgrad_kernel       Cout tile     staging vector 1/4     0                1 = a partial last slab
 //   8 xwgrad_halo_kernel  image width   4                      0                0
 //   9 xwgrad_stem_kernel  image width   1                      0                0
+//  10 xblock_kernel       image width   channels               1                weights: 0 the LDS ring, 1 LDS-DMA stages
+//  11 xblock_kernel STEM  image width   channels               1                as 10
 // slabs: split-K slabs (1) or weight-gradient slabs Z (7-9), else 1;  nclass: parity classes of the
 // launch (1);  lazy: an operand formed while staging (LazyBN x / LazyGrad dy)
 struct XLast {

@@ -188,14 +188,15 @@ DBA_EXPORT int dba_xsplit_w_batch(const void* desc, int n, int slots, void* stre
 
 DBA_EXPORT int dba_xfrag_w_batch(const void* desc, int n, int slots, void* stream) {
   const XFDesc* ds = (const XFDesc*)desc;
+  for (int i = 0; i < n; ++i)   // every descriptor before the first launch: a refusal writes nothing
+    if (ds[i].ncol <= 0 || ds[i].cs <= 0 || ds[i].ncol % 32 || ds[i].cs % 32 || ((ds[i].planes | ds[i].out) & 15))
+      return -105;
   for (int i0 = 0; i0 < n; i0 += kXSBatch) {
     XFBatch b{};
     b.n = std::min(kXSBatch, n - i0);
     long long nb = 0;
     for (int i = 0; i < b.n; ++i) {
       b.d[i] = ds[i0 + i];
-      if (b.d[i].ncol <= 0 || b.d[i].cs <= 0 || b.d[i].ncol % 32 || b.d[i].cs % 32 || ((b.d[i].planes | b.d[i].out) & 15))
-        return -105;
       b.d[i].boff = nb;
       nb += b.d[i].ncol * 9 * b.d[i].cs / 1024;
     }

@@ -552,7 +552,9 @@ DBA_EXPORT int dba_xblock_fwd(const float* x, long long x_gstride, float* out, l
            amax_x, amax_x_ld, amax_w1, amax_w2, amax_w_ld, amax_out, amax_out_ld,
            nullptr, 0, nullptr, 0, nullptr, w1f, w2f, wf_sstride};
   const dim3 grid((unsigned)(N * (kW / kTR)), G);
-  if (xstage_ok(kXStageBlockDefault, w1f, w2f, wf_sstride))
+  const bool gl = xstage_ok(kXStageBlockDefault, w1f, w2f, wf_sstride);
+  xg::last_launch() = XLast{10, kW, kC, 1, gl ? 1 : 0, 1, 1, 0};
+  if (gl)
     hipLaunchKernelGGL((xblock_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((xblock_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -583,7 +585,9 @@ DBA_EXPORT int dba_xblock_stem_fwd(const float* img, long long img_gstride, floa
            nullptr, 0, amax_w1, amax_w2, amax_w_ld, amax_out, amax_out_ld,
            w0p, w0_sstride, b0, b0_sstride, amax_w0, w1f, w2f, wf_sstride};
   const dim3 grid((unsigned)(N * (kW / kTR)), G);
-  if (xstage_ok(kXStageStemDefault, w1f, w2f, wf_sstride))
+  const bool gl = xstage_ok(kXStageStemDefault, w1f, w2f, wf_sstride);
+  xg::last_launch() = XLast{11, kW, kC, 1, gl ? 1 : 0, 1, 1, 0};
+  if (gl)
     hipLaunchKernelGGL((xblock_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((xblock_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, a);

@@ -27,6 +27,17 @@ namespace {
 // (x2[2h][2w] of the block's 128 output pixels, loaded and split at the start), with its own
 // fp16 scales (the accumulators are rescaled once, exactly) and pre-split weights; its output is
 // never written or read back as a residual (reference models/resnet_cifar.py:24-36).
+// The rescale ldexpf(acc, s_sc - s) is exact only while the result stays in range: the 3x3
+// accumulators hold up to 2^40 (576 x 3 products of planes below 2^15), so the shift is kept at or
+// below kScShiftMax = 80 by bounding the shortcut operand's scale exponent before its split:
+//     sx = max(-126, min(hexp(max |x2|), s + 80 - hexp(max |wsc|))),   s = hexp(max |a|) + hexp(max |w2|)
+// (-126: 2^sx stays a normal float; it binds only where the 3x3 sum itself is past fp32's range).
+// The bound binds only where the unbounded shift would pass 80: a shortcut whose products lie 2^80
+// or more below the 3x3's (an all-zero or vanishing x2, whose hexp is at the cap of 100).  Its split
+// then has the quantum 2^-24 2^-sx, so a shortcut product is resolved to 2^-89 of one unit of the
+// 3x3 accumulators, far below their fp32 rounding; every other input keeps its bits.  A negative
+// shift of any size only moves accumulators towards zero.
+constexpr int kScShiftMax = 80;
 template <int W, int CS, int BM, int BN, int WM, int WN, bool PRE = false, bool LZ = false, bool SC = false>
 __global__ __launch_bounds__(256) void xhalo_kernel(const XArgs a) {
   static_assert(!SC || (PRE && !LZ), "fused shortcut: evaluation, pre-split weights");
@@ -112,8 +123,9 @@ __global__ __launch_bounds__(256) void xhalo_kernel(const XArgs a) {
   hs.init(src_bits, amax_read(a.amax_w, a.amax_w_ld, slot));
   [[maybe_unused]] int s_sc = 0;
   if constexpr (SC) {
-    const int sx = hexp(amax_read(a.sc_amax_src, a.sc_amax_src_ld, g));
-    s_sc = sx + hexp(amax_read(a.sc_amax_w, a.sc_amax_w_ld, slot));
+    const int swsc = hexp(amax_read(a.sc_amax_w, a.sc_amax_w_ld, slot));
+    const int sx = max(-126, min(hexp(amax_read(a.sc_amax_src, a.sc_amax_src_ld, g)), hs.s + kScShiftMax - swsc));
+    s_sc = sx + swsc;
     const float m = __uint_as_float((uint32_t)(sx + 127) << 23);
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
@@ -338,7 +350,7 @@ int xhalo_go(const XArgs& a, int G, hipStream_t st) {
   XArgs b = a;
   b.tiles_n = ceil_div(a.Ncol, BN);
   const dim3 grid((unsigned)(a.N * (a.Ho / (BM / W)) * b.tiles_n), G, 1);
-  xg::last_launch() = XLast{2, W, CS, PRE, 0, 1, 1, LZ};
+  xg::last_launch() = XLast{2, W, CS, PRE, SC ? 1 : 0, 1, 1, LZ};
   hipLaunchKernelGGL((xhalo_kernel<W, CS, BM, BN, WM, WN, PRE, LZ, SC>), grid, dim3(256), 0, st, b);
   DBA_LAUNCH_CHECK();
 }

@@ -300,10 +300,19 @@ def last_conv_launch() -> dict:
     """The conv family's last main-kernel launch of this process (common.hpp ``XLast``): kernel kind,
     tile, staging vector, pre-split planes, split-K form, slabs, parity classes, lazy operand.  The
     tests check with it that a shape reached the kernel they name.  One unsynchronised record per
-    process: read it right after the call, on the calling thread, with no other thread launching convs."""
+    process: read it right after the call, on the calling thread, with no other thread launching convs.
+    ``kernel`` names the kind; ``form`` is 1 for the halo conv with the fused 1x1 shortcut (the
+    evaluation down-block) and, for the fused blocks (kinds 10 / 11), 1 for the LDS-DMA weight stages
+    and 0 for the LDS weight ring."""
     a = (ctypes.c_int * 8)()
     _L.dba_xconv_last_launch(ctypes.cast(a, ctypes.c_void_p))
-    return dict(zip(("kind", "tile", "vec", "pre", "form", "slabs", "nclass", "lazy"), (int(v) for v in a)))
+    rec = dict(zip(("kind", "tile", "vec", "pre", "form", "slabs", "nclass", "lazy"), (int(v) for v in a)))
+    rec["kernel"] = _LAUNCH_KINDS.get(rec["kind"], "")
+    return rec
+
+
+_LAUNCH_KINDS = {1: "xconv", 2: "xhalo", 3: "ximg", 4: "ximg2", 5: "xstage16", 6: "xstem", 7: "xwgrad", 8: "xwgrad_halo",
+                 9: "xwgrad_stem", 10: "xblock", 11: "xblock_stem"}
 
 
 def set_ximg(on: int) -> int:

@@ -33,8 +33,9 @@ def _weights(H, slots, dev, g, cout, cin):
     return w
 
 
-def _ab(H, G, dev, run, mode):
-    """run() under selector ``mode`` and 2 -> [(y, folded max |y|)] of both."""
+def _ab(H, G, dev, run, mode, forms=None):
+    """run() under selector ``mode`` and 2 -> [(y, folded max |y|)] of both.  ``forms``: the launch
+    record (kind, form) each of the two runs must leave (ops.hip.last_conv_launch)."""
     outs = []
     prev = H.set_xstage(-1)
     try:
@@ -43,6 +44,9 @@ def _ab(H, G, dev, run, mode):
             assert H.set_xstage(-1) == m
             with H.amax_arena(G, dev):
                 y = run()
+                if forms is not None:
+                    l = H.last_conv_launch()
+                    assert (l["kind"], l["form"]) == forms[len(outs)], (m, l)
                 outs.append((y, y._dba_amax.clone()))
     finally:
         H.set_xstage(prev)
@@ -101,7 +105,11 @@ def test_block_stages_bits_equal_ring(H, G, N, nv, scale, stem, mode):
     dev = torch.device("cuda")
     args = _block_inputs(G, N, nv, scale, stem, dev, H)
     assert args[3]._dba_fplanes.shape == (2, 2 * 32 * 288) and args[5]._dba_fplanes.shape == (2, 2 * 32 * 288)
-    _assert_equal(_ab(H, G, dev, _block_run(H, stem, *args), mode), G, N, nv)
+    # the selector reached the weight form it names: staged (form 1) under 3, and under 1 where the
+    # kernel's default is on (the plain block; the stem variant's is off); the ring (form 0) under 2
+    kind = 11 if stem else 10
+    staged = 1 if (mode == 3 or not stem) else 0
+    _assert_equal(_ab(H, G, dev, _block_run(H, stem, *args), mode, ((kind, staged), (kind, 0))), G, N, nv)
 
 
 @pytest.mark.parametrize("stem", [False, True])
@@ -112,7 +120,8 @@ def test_block_without_fragment_planes_runs_the_ring(H, stem):
     G, N, nv = 2, 3, (3, 1)
     args = _block_inputs(G, N, nv, 1.0, stem, dev, H)
     del args[5]._dba_fplanes
-    _assert_equal(_ab(H, G, dev, _block_run(H, stem, *args), 3), G, N, nv)
+    kind = 11 if stem else 10
+    _assert_equal(_ab(H, G, dev, _block_run(H, stem, *args), 3, ((kind, 0), (kind, 0))), G, N, nv)
 
 
 # the 16-wide conv (W 16, 64 -> 64): with residual and ReLU, a partly valid replica; one image
